@@ -1,6 +1,6 @@
 """Bloom build + probe benchmark (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2c3|c4|c5|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2c3|c4|c5|...] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (RCCL over xGMI)
 
 `--gpus N` with N > 1 and no launcher environment spawns the N rank processes itself
@@ -18,7 +18,7 @@ arrives spread over the ranks, 1/N per GPU, each rank packs its part and an RCCL
 replicates the whole batch ahead of the step that probes it, so every xGMI link carries 1/N of
 it (measured on the default N > 1 line as its all_gather_spread secondary).  Per-GPU work is
 fixed as N grows (weak scaling); value = (build + probe keys over all ranks) / max-over-ranks
-wall time, inputs already resident in HBM.  At N > 1 the default line also runs the north
+wall time, inputs already resident in HBM.  At N > 1 the default line with --full also runs the north
 star's C5 (c5: 64 filters sharded over the ranks, a new batch broadcast every step; c5_spread;
 c5_2d) in the same processes after the headline (dist_variants).
 c4: the same with variable-length keys (8-256 B, zipf); no broadcast.
@@ -29,9 +29,16 @@ c5: 64 compaction-sized filters (100K keys each) sharded over the ranks, a 10M-k
 broadcast from rank 0, multi-filter probe, answer planes gathered to rank 0 (strong scaling;
 value = batch keys / s).
 
-Printed (rank 0): one JSON line with the metric, a `roofline` object for the dominant kernel
-(algorithmic bytes / hipEvent-measured launch time on the launch stream) and a `cpu_baseline`
-(the oracle C restatement timed on this host, rank 0, N = 1 only).
+Printed (rank 0): one JSON line with the metric and a `roofline` object for the dominant kernel
+(algorithmic bytes / hipEvent-measured launch time on the launch stream, sampled inside the
+timed steps).
+
+A plain run sets up, warms up, times the K steps, writes its outputs when --dump-outputs DIR is
+given (what the last timed step computed, as DIR/<name>.npy) and prints the line.  --full adds
+everything that takes work of its own after the timed steps: `parity` against the golden digests,
+`kernel_timing` (--kernel-reps further steps with every launch timed), `host_inclusive`, the
+`cpu_baseline` (the oracle C restatement timed on this host, rank 0, N = 1 only), the `secondary`
+lines of the other configs (N = 1) and the same-process variants of the N > 1 line.
 """
 from __future__ import annotations
 
@@ -105,9 +112,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=50,
                     help="untimed steps first: the GPU's clocks rise over the first ~50 steps of this load "
                          "(0.467-0.470 ms per step after 3, 0.439-0.442 after 50-200: profiles/r06m_warmup_steps.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline figure: parity against the "
+                         "golden digests, kernel_timing, host_inclusive, cpu_baseline, the secondary lines (N = 1) "
+                         "and the N > 1 line's same-process variants (each can be switched off with its --no-* "
+                         "option); without it the run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's arrays, as a "
+                         "caller receives them) to DIR/<name>.npy in float32 / float64, at most 64 MB in all "
+                         "(a larger array as a fixed, seeded sample); inputs are the same from run to run")
     ap.add_argument("--kernel-reps", type=int, default=20,
-                    help="after the timed steps (outside their wall clock), this many more steps with every launch "
-                         "timed by HIP events: the kernel_timing median / min (SURVEY 8(d)); 0 skips; one GPU only")
+                    help="--full: after the timed steps (outside their wall clock), this many more steps with every "
+                         "launch timed by HIP events: the kernel_timing median / min (SURVEY 8(d)); 0 skips; one GPU only")
     ap.add_argument("--config", default="c2c3", choices=["c2c3", "c4", "c5", "c5_2d", "lsm", "lsm_wide", "route",
                                                            "wal", "many", "c2_sharded", "c3_partitioned", "flush"])
     ap.add_argument("--keys", type=int, default=10_000_000)
@@ -144,7 +160,13 @@ def parse():
                     help="c2c3/c4: build step j+1 (second filter buffer, own stream) while step j probes")
     for o in OPTIONS:
         ap.add_argument("--" + o.replace("_", "-"), type=int, default=None)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: nothing after the timed steps but the dump and the line
+        args.kernel_reps = 0
+        args.no_cpu_baseline = args.no_host_inclusive = args.no_secondary = True
+    if args.dump_outputs and args.config == "flush":
+        ap.error("--dump-outputs: --config flush runs in harness/flush_bench.c, which reports digests, not arrays")
+    return args
 
 
 class Setup:
@@ -166,6 +188,7 @@ class Setup:
     bcast_prologue = None # rank 0, before the loop: produce(b, buf) fills the buffer of batch b < lead
     pmc_key = None        # profiles/pmc_r01.json entry whose per-launch traffic applies (None: config name)
     pipe = None           # a ready pipeline (c5_2d's dist_probe.GridPipeline) instead of a broadcast one
+    outputs = None        # outputs(j): {name: array} step j left on this rank for its caller (--dump-outputs)
 
 
 def setup_c2c3(args, seb, kg, torch, dev, rank, world, dist):
@@ -288,6 +311,7 @@ def setup_c2c3(args, seb, kg, torch, dev, rank, world, dist):
                 else f"MISMATCH build={ok_b} probe={ok_p}")
 
     st.build, st.probe, st.parity = build, probe, parity
+    st.outputs = lambda j: {"filter_bits": seb.words_to_bits(st.wbufs[j % len(st.wbufs)], m), "answers": st.out}
     return st
 
 
@@ -330,6 +354,7 @@ def setup_c2_sharded(args, seb, kg, torch, dev, rank, world, dist):
             else "MISMATCH filter"
 
     st.probe, st.parity = step, parity
+    st.outputs = lambda j: {"filter_bits": seb.words_to_bits(st.words, m)}
     return st
 
 
@@ -373,6 +398,7 @@ def setup_c3_partitioned(args, seb, kg, torch, dev, rank, world, dist):
         return "bit-exact (sha256 of the 10M gathered answers matches tests/golden C3)" if ok else "MISMATCH answers"
 
     st.probe, st.parity = step, parity
+    st.outputs = lambda j: {"answers": st.ans}
     return st
 
 
@@ -416,6 +442,7 @@ def setup_c4(args, seb, kg, torch, dev, rank, world, dist):
     st.build = build
     st.probe = lambda j, buf, target: seb.dev_probe(st.pk[j % 2], st.wbufs[j % len(st.wbufs)], m, k, st.out)
     st.parity = parity
+    st.outputs = lambda j: {"filter_bits": seb.words_to_bits(st.wbufs[j % len(st.wbufs)], m), "answers": st.out}
     return st
 
 
@@ -557,6 +584,7 @@ def setup_c5(args, seb, kg, torch, dev, rank, world, dist):
         return "bit-exact (sha256 of the 10M u64 masks matches tests/golden c5)" if ok else "MISMATCH masks"
 
     st.probe, st.parity = probe, parity
+    st.outputs = lambda j: {"masks": dp.assemble_mask(st.planes if world > 1 else [st.plane], nf)}
     return st
 
 
@@ -611,6 +639,7 @@ def setup_c5_2d(args, seb, kg, torch, dev, rank, world, dist):
             return "bit-exact (sha256 of the 10M u64 masks matches tests/golden c5)" if ok else "MISMATCH masks"
 
         st.probe, st.parity = probe, parity
+        st.outputs = lambda j: {"masks": st.plane}
         return st
     if not (k == 7 and m < (1 << 29)):
         raise SystemExit("c5_2d at N > 1 sends packed residues: needs k == 7 and m < 2^29")
@@ -643,6 +672,7 @@ def setup_c5_2d(args, seb, kg, torch, dev, rank, world, dist):
                 else "MISMATCH masks")
 
     st.probe, st.parity = probe, parity
+    st.outputs = lambda j: {"masks": ex.mask(j)}
     return st
 
 
@@ -704,6 +734,7 @@ def setup_lsm(args, seb, kg, torch, dev, rank, world, dist):
         return "bit-exact (sha256 of the 10M MultiGet masks matches tests/golden lsm)" if ok else "MISMATCH masks"
 
     st.parity = parity
+    st.outputs = lambda j: {"candidate_rows": st.rows} if wide else {"masks": st.mask}
     return st
 
 
@@ -737,6 +768,7 @@ def setup_route(args, seb, kg, torch, dev, rank, world, dist):
             else "MISMATCH partition"
 
     st.parity = parity
+    st.outputs = lambda j: {"perm": st.perm, "shard_begin": st.begin}
     return st
 
 
@@ -777,6 +809,7 @@ def setup_many(args, seb, kg, torch, dev, rank, world, dist):
             else "MISMATCH filters"
 
     st.probe, st.parity = build_many, parity
+    st.outputs = lambda j: {"filter_bits": np.stack([seb.words_to_bits(w, m) for w, _, _ in st.filters])}
     return st
 
 
@@ -814,12 +847,56 @@ def setup_wal(args, seb, kg, torch, dev, rank, world, dist):
             if ok else "MISMATCH crc"
 
     st.parity = parity
+    st.outputs = lambda j: {"crc": st.crc, "ok": st.ok}
     return st
 
 
 SETUPS = {"c2c3": setup_c2c3, "c4": setup_c4, "c5": setup_c5, "c5_2d": setup_c5_2d, "lsm": setup_lsm,
           "lsm_wide": setup_lsm, "route": setup_route, "many": setup_many, "wal": setup_wal,
           "c2_sharded": setup_c2_sharded, "c3_partitioned": setup_c3_partitioned}
+
+
+DUMP_BUDGET = 64_000_000  # bytes of .npy files per --dump-outputs run
+DUMP_SEED = 12345         # the sample of an output too large to write whole
+
+
+def exact_float(a: np.ndarray) -> np.ndarray:
+    """An integer array as floats that hold every value exactly: up to 16-bit integers as
+    float32, 32-bit as float64 of the unsigned word, 64-bit as float64 of its two little-endian
+    unsigned 32-bit halves (low half first)."""
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.dtype.kind == "f":
+        return a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+    if a.dtype.itemsize <= 2:
+        return a.view(f"u{a.dtype.itemsize}").astype(np.float32)
+    return a.view("<u4").astype(np.float64)
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """--dump-outputs: each array to path/<name>.npy (exact_float), DUMP_BUDGET bytes in all.  The
+    budget is shared smallest first: an array that fits its share is written whole; a larger one
+    as the elements at a fixed sorted sample of positions (np.random.default_rng(DUMP_SEED), the
+    same for every run of the same shapes), so two builds' files compare element for element.
+    Bit arrays (uint8 bytes of a filter) are packed four to a 32-bit word first."""
+    os.makedirs(path, exist_ok=True)
+    flat = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).reshape(-1)
+        if name == "filter_bits":  # 4 bytes per float64 instead of 1 per float32
+            a = np.concatenate([a, np.zeros(-a.size % 4, np.uint8)]).view("<u4")
+        flat[name] = a
+    per = {name: exact_float(a[:1]).nbytes if a.size else 1 for name, a in flat.items()}  # bytes written per element
+    left, report = DUMP_BUDGET - 1024 * len(flat), {}  # the .npy headers
+    for i, name in enumerate(sorted(flat, key=lambda x: flat[x].size * per[x])):
+        a = flat[name]
+        keep = min(a.size, (left // (len(flat) - i)) // per[name])
+        if keep < a.size:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=keep, replace=False))]
+        out = exact_float(a)
+        np.save(os.path.join(path, name + ".npy"), out)
+        left -= out.nbytes
+        report[name] = {"elements": int(flat[name].size), "written": int(keep), "dtype": str(out.dtype)}
+    return report
 
 
 def free_port() -> int:
@@ -1058,12 +1135,12 @@ def main():
             seb.set_option(o, v)
 
     st = SETUPS[args.config](args, seb, kg, torch, dev, rank, world, dist)
-    run = timed_run(args, st, seb, torch, dist, world, rank, dev)
+    run = timed_run(args, st, seb, torch, dist, world, rank, dev, dump=args.dump_outputs if rank == 0 else None)
     # Parity of the last timed step's outputs, checked after the timed region: a large pageable
     # D2H (.cpu()) delays the next kernel launch by ~20 ms on this runtime (tools/dbg_sharded_timing.py),
     # which must not land inside the timed steps.
     torch.cuda.synchronize()
-    parity = st.parity(args.warmup + args.steps - 1)
+    parity = st.parity(args.warmup + args.steps - 1) if args.full else None
     elapsed, kern_ms, bcast, overlap = run["elapsed"], run["kern_ms"], run["bcast"], run["overlap"]
     # Each rank's record (GPU PCI address, communicator size and an all-reduce of ones over it, its
     # launch and broadcast-wait times), gathered to rank 0: the line proves what it ran on.
@@ -1095,7 +1172,8 @@ def main():
             **{f"{name}_gkeys_s": round(st.n / (ms * 1e-3) / 1e9, 3) for name, ms in kern_ms.items()},
             **{f"{name}_ms": round(ms, 4) for name, ms in kern_ms.items()},
             "roofline": roofline_of(st, kern_ms, args.config),
-            "parity": parity,
+            **({"parity": parity} if args.full else {}),
+            **({"outputs": {"dir": args.dump_outputs, "arrays": run["dumped"]}} if run["dumped"] else {}),
             **({"kernel_timing": run["kernel_timing"]} if run["kernel_timing"] else {}),
             **({"broadcast": bcast} if bcast else {}),
             **extra,
@@ -1304,10 +1382,11 @@ def run_variant(args, cfg, over, note, seb, kg, torch, dist, world, rank, local,
     return out
 
 
-def timed_run(args, st, seb, torch, dist, world, rank, dev):
+def timed_run(args, st, seb, torch, dist, world, rank, dev, dump=None):
     """W untimed warm-up steps, then exactly K timed steps between a barrier + synchronize on
     both sides; the max over ranks of the wall time, the sampled launch durations and (a resident
-    batch at N > 1) the batch's broadcast timed on its own."""
+    batch at N > 1) the batch's broadcast timed on its own.  `dump`: a directory for the last timed
+    step's outputs (dump_outputs), written once the wall clock has stopped."""
     torch.cuda.synchronize()
     overlap = bool(args.overlap) and st.build is not None
     sp = torch.cuda.current_stream()                          # probe (and broadcast) stream
@@ -1410,6 +1489,7 @@ def timed_run(args, st, seb, torch, dist, world, rank, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(dump, st.outputs(args.warmup + args.steps - 1)) if dump else None
 
     kern_ms = {(st.probe_name if name == "probe" else name): float(np.mean([a.elapsed_ms(b) for a, b in pairs]))
                for name, pairs in times.items() if pairs}
@@ -1451,7 +1531,7 @@ def timed_run(args, st, seb, torch, dist, world, rank, dev):
     wait = {"wait_ms": float(np.mean([a.elapsed_ms(b) for a, b in waits])) if waits else None,
             "wait_host_ms": float(np.mean(host_waits)) * 1e3 if host_waits else None}
     return {"elapsed": elapsed, "elapsed_own": own, "kern_ms": kern_ms, "bcast": bcast, "overlap": overlap,
-            "kernel_timing": kernel_timing, **wait}
+            "kernel_timing": kernel_timing, "dumped": dumped, **wait}
 
 
 SECONDARY = (("c4", ["--steps", "20", "--warmup", "30"]),  # each child a fresh context: clocks ramp again
@@ -1468,7 +1548,7 @@ def secondary_lines():
     compact summary of each child's JSON line; a failure is recorded, never fatal."""
     out = []
     for cfg, extra in SECONDARY:
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--no-secondary", *extra]
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", cfg, "--no-secondary", *extra]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
             line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

@@ -26,7 +26,7 @@ def _run(args, env=None, timeout=120):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_gpus_n_spawns_n_ranks(n):
-    r = _run(["--gpus", str(n), "--launch-check"])
+    r = _run(["--gpus", str(n), "--launch-check", "--full"])
     assert r.returncode == 0, r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1  # rank 0 alone prints
@@ -71,7 +71,7 @@ def test_gpus_n_spawns_n_ranks(n):
 def test_variant_failing_on_every_rank_is_reported_and_the_line_prints():
     """A variant that raises on every rank (e.g. an operation the backend rejects) becomes an
     error entry; the variants after it still run and rank 0 still prints its one line."""
-    r = _run(["--gpus", "2", "--launch-check"], env=_env(SEB_BENCH_FAIL_VARIANT="c5"))
+    r = _run(["--gpus", "2", "--launch-check", "--full"], env=_env(SEB_BENCH_FAIL_VARIANT="c5"))
     assert r.returncode == 0, r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -86,7 +86,7 @@ def test_variant_failing_on_one_rank_ends_the_run():
     """A variant that fails on one rank only leaves its peers in a collective it never joins: the
     failing rank's bounded barrier on the gloo side group times out and the run exits non-zero
     (as an uncaught error would) instead of hanging."""
-    r = _run(["--gpus", "2", "--launch-check"],
+    r = _run(["--gpus", "2", "--launch-check", "--full"],
              env=_env(SEB_BENCH_FAIL_VARIANT="c5@1", SEB_BENCH_VARIANT_VOTE_S="5"), timeout=180)
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -157,6 +157,40 @@ def test_rccl_needs_n_gpus(monkeypatch):
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
     args = type("A", (), {"gpus": 4, "launch_check": False, "dist_backend": "nccl"})()
     assert bench.launch_ranks(args, []) == 3  # refuses before starting any rank
+
+
+def test_dump_outputs_exact_and_bounded(tmp_path):
+    """--dump-outputs' writer: float files that hold every integer exactly, 64 MB at most in all,
+    an array past its share as the same sorted sample in every run, the others whole."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    bits = rng.integers(0, 256, 1_000_003, dtype=np.uint8)  # not a multiple of 4 bytes
+    answers = rng.integers(0, 2, 300_000, dtype=np.uint8)
+    masks = rng.integers(-2**63, 2**63 - 1, 5_000_000, dtype=np.int64)  # 80 MB as float64 halves
+    begin = np.arange(257, dtype=np.int64) << 33
+    for d in ("a", "b"):
+        rep = bench.dump_outputs(str(tmp_path / d), {"filter_bits": bits, "answers": answers, "masks": masks,
+                                                     "shard_begin": begin})
+    files = {f: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sorted(files) == ["answers.npy", "filter_bits.npy", "masks.npy", "shard_begin.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 64_000_000
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert files["answers.npy"].dtype == np.float32 and np.array_equal(files["answers.npy"], answers)
+    back = files["filter_bits.npy"].astype("<u4").view(np.uint8)
+    assert np.array_equal(back[:bits.size], bits) and not back[bits.size:].any()
+    assert np.array_equal(files["shard_begin.npy"].astype("<u4").view("<i8"), begin)
+    assert rep["masks"]["written"] < rep["masks"]["elements"] == masks.size
+    assert rep["masks"]["written"] * 16 > 50_000_000  # the sample takes what the small ones left
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(masks.size, rep["masks"]["written"], replace=False))
+    assert np.array_equal(files["masks.npy"].astype("<u4").view("<i8"), masks[pos])
+    for f in files:  # the same positions and values in every run
+        assert np.array_equal(np.load(tmp_path / "a" / f), files[f])
 
 
 def test_rank_envs():

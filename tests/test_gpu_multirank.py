@@ -28,7 +28,7 @@ BENCH = os.path.join(ROOT, "bench.py")
 def _bench(*args, timeout=170):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup",
                         "2", "--time-every", "1", *args], capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

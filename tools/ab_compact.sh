@@ -5,7 +5,7 @@ set -e
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/abc
 mkdir -p "$OUT"
-ARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive --no-secondary"
+ARGS="--full --steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive --no-secondary"
 for r in 1 2; do
   for c in 1 0; do
     timeout -k 10 120 python3 "$ROOT/bench.py" $ARGS --probe-compact $c > "$OUT/c${c}_$r.json"

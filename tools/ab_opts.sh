@@ -6,7 +6,7 @@ TAG=$1
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/abo_$TAG
 mkdir -p "$OUT"
-ARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive --no-secondary ${EXTRA:-}"
+ARGS="--full --steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive --no-secondary ${EXTRA:-}"
 IFS=';' read -ra VS <<< "$VARIANTS"
 for r in 1 2; do
   for v in "${VS[@]}"; do

@@ -4,7 +4,7 @@ set -e
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/abp
 mkdir -p "$OUT"
-ARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive --no-secondary"
+ARGS="--full --steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive --no-secondary"
 for p in ${PHASES:-3 4 5 6}; do
   for c in ${COMPACT:-1}; do
     timeout -k 10 120 python3 "$ROOT/bench.py" $ARGS --probe-compact $c --probe-phases $p > "$OUT/p${p}_c${c}.json"

@@ -4,7 +4,7 @@ OUT=gpurun_out/r6sl; mkdir -p $OUT
 for r in 1 2 3; do
   for name in product sl22 sl20; do
     lib=tools/ab_lib/$name/libseb_bloom.so; [ $name = product ] && lib=storage-engines_amd/lib/libseb_bloom.so
-    SEB_LIB_PATH=$lib timeout -k 10 200 python bench.py --config c5 --no-cpu-baseline --no-host-inclusive --no-secondary > $OUT/$name.$r.json 2> $OUT/$name.$r.err || exit 1
+    SEB_LIB_PATH=$lib timeout -k 10 200 python bench.py --full --config c5 --no-cpu-baseline --no-host-inclusive --no-secondary > $OUT/$name.$r.json 2> $OUT/$name.$r.err || exit 1
   done
 done
 python3 - <<'PY'

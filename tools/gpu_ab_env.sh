@@ -13,7 +13,7 @@ OUT=$ROOT/gpurun_out/abenv_$TAG
 mkdir -p "$OUT"
 for r in 1 2 3; do
   for i in "${!V[@]}"; do
-    env ${V[$i]} timeout -k 10 200 python "$ROOT/bench.py" --steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive \
+    env ${V[$i]} timeout -k 10 200 python "$ROOT/bench.py" --full --steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive \
         --no-secondary "$@" > "$OUT/v$i.$r.json" 2> "$OUT/v$i.$r.err" || exit 1
   done
 done

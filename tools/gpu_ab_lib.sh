@@ -7,9 +7,9 @@ TAG=$1; ALT=$2; shift 2
 OUT=$ROOT/gpurun_out/ab_$TAG
 mkdir -p "$OUT"
 for r in 1 2 3; do
-  timeout -k 10 200 python "$ROOT/bench.py" --steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive \
+  timeout -k 10 200 python "$ROOT/bench.py" --full --steps 30 --warmup 5 --no-cpu-baseline --no-host-inclusive \
       --no-secondary "$@" > "$OUT/new$r.json" 2> "$OUT/new$r.err" || exit 1
-  SEB_LIB_PATH=$ROOT/$ALT timeout -k 10 200 python "$ROOT/bench.py" --steps 30 --warmup 5 --no-cpu-baseline \
+  SEB_LIB_PATH=$ROOT/$ALT timeout -k 10 200 python "$ROOT/bench.py" --full --steps 30 --warmup 5 --no-cpu-baseline \
       --no-host-inclusive --no-secondary "$@" > "$OUT/old$r.json" 2> "$OUT/old$r.err" || exit 1
 done
 python3 - "$OUT" <<'PY'

@@ -11,8 +11,8 @@ tail -1 $OUT/tests.log
 PREV=$ROOT/tools/ab_lib/prev2/libseb_bloom.so
 for r in 1 2; do
   for cfg in ${CFGS:-c4 lsm lsm_wide}; do
-    timeout -k 10 200 python bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline > $OUT/new_$cfg.$r.json 2>$OUT/err || exit 1
-    SEB_LIB_PATH=$PREV timeout -k 10 200 python bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prev_$cfg.$r.json 2>$OUT/err || exit 1
+    timeout -k 10 200 python bench.py --full --config $cfg --steps 20 --warmup 3 --no-cpu-baseline > $OUT/new_$cfg.$r.json 2>$OUT/err || exit 1
+    SEB_LIB_PATH=$PREV timeout -k 10 200 python bench.py --full --config $cfg --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prev_$cfg.$r.json 2>$OUT/err || exit 1
   done
 done
 OUT=$OUT python3 - <<'PY'

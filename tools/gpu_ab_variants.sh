@@ -10,7 +10,7 @@ mkdir -p $OUT
 for r in $(seq 1 ${REPS:-2}); do
   for cfg in ${CFGS:-lsm}; do
     for v in ${VARIANTS:-head}; do
-      SEB_LIB_PATH=$ROOT/tools/ab_lib/$v/libseb_bloom.so timeout -k 10 200 python bench.py --config $cfg --steps 20 \
+      SEB_LIB_PATH=$ROOT/tools/ab_lib/$v/libseb_bloom.so timeout -k 10 200 python bench.py --full --config $cfg --steps 20 \
           --warmup 3 --no-cpu-baseline > $OUT/${v}_$cfg.$r.json 2>$OUT/err || { tail -20 $OUT/err; exit 1; }
     done
   done

@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 tail -1 $OUT/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['parity'][:30], d['roofline']['frac'])

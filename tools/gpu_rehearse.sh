@@ -13,7 +13,7 @@ for cfg in "c2c3" "c2c3 --batch-origin root" "c2c3 --bcast keys" "c5" "c5_2d" "c
     tag=$(echo "$cfg" | tr ' ' '_' | tr -d '-')
     port=$((port + 1))
     timeout -k 10 240 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-        --master-port $port "$ROOT/bench.py" --gpus "$N" --steps 4 --warmup 2 --dist-backend gloo \
+        --master-port $port "$ROOT/bench.py" --full --gpus "$N" --steps 4 --warmup 2 --dist-backend gloo \
         --no-cpu-baseline --no-host-inclusive --config $cfg > "$OUT/rehearse_${N}_${tag}.json" 2> "$OUT/rehearse_${N}_${tag}.err"
     python3 -c "
 import json, sys

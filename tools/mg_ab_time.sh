@@ -12,7 +12,7 @@ for r in $(seq 1 "$ROUNDS"); do
     lib=$ROOT/tools/ab_lib/$name/libseb_bloom.so
     [ "$name" = product ] && lib=$ROOT/storage-engines_amd/lib/libseb_bloom.so
     for c in lsm lsm_wide; do
-      SEB_LIB_PATH=$lib timeout -k 10 200 python3 "$ROOT/bench.py" --config $c --no-cpu-baseline \
+      SEB_LIB_PATH=$lib timeout -k 10 200 python3 "$ROOT/bench.py" --full --config $c --no-cpu-baseline \
         > "$OUT/$name.$c.$r.json" 2> "$OUT/$name.$c.$r.err"
     done
   done
