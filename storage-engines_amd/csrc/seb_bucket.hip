@@ -284,7 +284,7 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter_bins(Src src, uint64_t 
 #pragma unroll
             for (int r = 0; r < KPT; ++r) {
                 const uint64_t i = r0 + (uint64_t)r * THREADS + threadIdx.x;
-                if (i < r1) kv[r] = src.load(i);
+                kv[r] = src.load(i < r1 ? i : r0);  // past the round: the tile's first key (t0 < n), never claimed
             }
         }
     };
@@ -299,17 +299,31 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter_bins(Src src, uint64_t 
         bool pv[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) pv[g] = false;
-        auto write_bins = [&](const uint32_t (&pw)[7], const uint32_t (&sw)[7]) {
+        // The 7 bin entries of a key go out unconditionally: a claim past the bin, and every entry of
+        // a lane with no key this step (`on` false), lands in a scratch word.  The key's largest slot
+        // is tested once; only a key with a claim past its bin (the Poisson tail above) walks its
+        // positions again, in a loop that is not unrolled, so each call site carries one copy of the
+        // region-store and overflow path, not seven.
+        auto write_bins = [&](bool on, const uint32_t (&pw)[7], const uint32_t (&sw)[7]) {
+            uint32_t most = 0u;
 #pragma unroll
             for (int q = 0; q < 7; ++q) {
                 const uint32_t p = pw[q], sl = sw[q], b = p >> kBktShift;
-                bins[sl < S ? b * S + sl : nb * S + 4 * nb] = (uint16_t)p;  // past the bin: a scratch word
-                if (sl >= S) {  // rare: straight to the region slot (the fill is fixed this round)
-                    const uint32_t e = fill[b] + sl;
-                    if (e < cap)
-                        regions[(uint64_t)(b * ntiles + t) * cap + e] = (uint16_t)p;
-                    else
-                        bins_overflow_or(ovw, b, p & 0xffffu);
+                bins[on ? (sl < S ? b * S + sl : nb * S + 4 * nb) : nb * S + 4 * nb] = (uint16_t)p;
+                most = most > sl ? most : sl;
+            }
+            if (on && most >= S) {  // rare: straight to the region slot (the fill is fixed this round)
+#pragma nounroll
+                for (int q = 0; q < 7; ++q) {
+                    uint32_t p = pw[0], sl = sw[0];
+#pragma unroll
+                    for (int j = 1; j < 7; ++j) {
+                        p = q == j ? pw[j] : p;
+                        sl = q == j ? sw[j] : sl;
+                    }
+                    const uint32_t b = p >> kBktShift, e = fill[b] + sl;
+                    if (sl >= S && e < cap) regions[(uint64_t)(b * ntiles + t) * cap + e] = (uint16_t)p;
+                    if (sl >= S && e >= cap) bins_overflow_or(ovw, b, p & 0xffffu);
                 }
             }
         };
@@ -349,6 +363,8 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter_bins(Src src, uint64_t 
                     const uint64_t in = i + round_keys;
                     if (valid[g] && k1 < t1 && in < (k1 + round_keys < t1 ? k1 + round_keys : t1)) kv[r] = src.load(in);
                 }
+#pragma unroll
+                for (int q = 0; q < 7; ++q) sl[g][q] = 0u;
                 if (valid[g]) {
 #pragma unroll
                     for (int q = 0; q < 7; ++q) sl[g][q] = atomicAdd(&cnt[pos[g][q] >> kBktShift], 1u);
@@ -356,7 +372,7 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter_bins(Src src, uint64_t 
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                if (pv[g]) write_bins(pp[g], ps[g]);
+                if (st > 0) write_bins(pv[g], pp[g], ps[g]);
 #pragma unroll
                 for (int q = 0; q < 7; ++q) {
                     pp[g][q] = pos[g][q];
@@ -367,7 +383,7 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter_bins(Src src, uint64_t 
         }
 #pragma unroll
         for (int g = 0; g < G; ++g)
-            if (pv[g]) write_bins(pp[g], ps[g]);
+            write_bins(pv[g], pp[g], ps[g]);
         __syncthreads();
         // write-out: a bucket's S/8 chunks on S/8 adjacent lanes of one wave (64/(S/8) buckets per
         // wave; with S = 48, lanes 60-63 idle), so the lane that advances the bucket's fill runs in

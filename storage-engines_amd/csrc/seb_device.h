@@ -253,6 +253,46 @@ __device__ __forceinline__ uint32_t mod_m31(uint64_t x, uint32_t m, uint64_t mu)
     return s < r ? s : r;
 }
 
+// One step of the residue recurrence: (x + a) mod m, given the addend negated, na = m - a.
+//   step_mod(x, na, m) = min(x - na, x - na + m)   in u32 arithmetic (both wrap mod 2^32).
+// Exact for m < 2^31, x < m, 1 <= na <= m.  Let t = x - na mod 2^32 and u = t + m mod 2^32.
+//   x >= na: t = x - na lies in [0, m - 1] and u = t + m < 2m < 2^32 does not wrap, so u > t and the
+//            minimum is t = x + a - m, which is (x + a) mod m because x + a = t + m >= m.
+//   x <  na: t = 2^32 - (na - x) with 1 <= na - x <= m, so t >= 2^32 - m > 2^31; u wraps to
+//            x + m - na = x + a, which lies in [0, m - 1], below 2^31 < t: the minimum is u = x + a < m.
+// The minimum is an opaque v_min_u32: written as a compare and select, the compiler turns the whole
+// step back into v_sub_co_u32, two wait states for VCC, v_cndmask, v_add_u32 (5 issue slots for 3).
+__device__ __forceinline__ uint32_t step_mod(uint32_t x, uint32_t na, uint32_t m) {
+    const uint32_t t = x - na, u = t + m;
+    uint32_t r;
+    asm("v_min_u32 %0, %1, %2" : "=v"(r) : "v"(t), "v"(u));
+    return r;
+}
+
+// The negated step addends of a key: nb = m - b for a step whose u64 sum h1 + q*h2 does not wrap,
+// nd = m - ((b - c) mod m) for one that does (c = 2^64 mod m), both in [1, m].
+__device__ __forceinline__ void step_addends(uint32_t b, uint32_t m, uint32_t c, uint32_t &nb, uint32_t &nd) {
+    nb = m - b;
+    // -nd = (b >= c ? b - c : b - c + m) - m = max(t, t - m) with t = b - c, in u32 arithmetic (b, c < m
+    // < 2^31): for b >= c, t < m and t - m wraps to at least 2^32 - m, the larger; for b < c both
+    // wrap, t >= 2^32 - m + 1 stays above t - m >= 2^32 - 2m + 1.  An opaque v_max_u32 for
+    // step_mod's reason: 3 instructions where the compare and select take 5.
+    const uint32_t t = b - c, u = t - m;
+    uint32_t mnd;
+    asm("v_max_u32 %0, %1, %2" : "=v"(mnd) : "v"(t), "v"(u));
+    nd = 0u - mnd;
+}
+
+// nd where bit `bit` of the flag word f is set, else nb: the bit spread to a mask (v_bfe_i32) and
+// one bitfield insert.  (As a C++ select the compiler makes it v_and, v_cmp, two wait states for
+// VCC and v_cndmask.)
+__device__ __forceinline__ uint32_t pick_addend(uint32_t f, int bit, uint32_t nb, uint32_t nd) {
+    const uint32_t mask = (uint32_t)((int32_t)(f << (31 - bit)) >> 31);
+    uint32_t r;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(nd), "v"(nb));
+    return r;
+}
+
 // Calls f(i, pos_i) for i < k with pos_i = (h1 + i*h2 mod 2^64) mod m, bit-exact with
 // lsm/bloom.go:64.  Residues advance incrementally: r_{i+1} = r_i + (h2 mod m), minus
 // (2^64 mod m) whenever the u64 sum h1 + (i+1)*h2 wraps.  M32: m < kM32Limit -> u32 residues.
@@ -266,20 +306,17 @@ __device__ __forceinline__ void for_positions(uint64_t h1, uint64_t h2, const Mo
         uint32_t r = mod_m31(h1, m, md.mu);
         const uint32_t b = mod_m31(h2, m, md.mu);
         // Step addend: b, or (b - c) mod m when the u64 sum wraps.  Kept negated (m - a, in
-        // [1, m]) so r + a mod m is one subtract, one compare and a conditional add of m, with
-        // no u32 overflow for any m < 2^31.
-        const uint32_t nb = m - b;
-        const uint32_t bc = b >= c ? b - c : b + (m - c);
-        const uint32_t nd = m - bc;
+        // [1, m]) so r + a mod m is step_mod's subtract, add and minimum, with no u32 overflow
+        // for any m < 2^31.
+        uint32_t nb, nd;
+        step_addends(b, m, c, nb, nd);
         f(0u, (uint64_t)r);
 #pragma unroll
         for (uint32_t i = 1; i < k; ++i) {
-            uint64_t xn = x + h2;
-            const bool carry = xn < x;
+            unsigned long long xn;
+            const bool carry = __builtin_uaddll_overflow(x, h2, &xn);  // the add's own carry-out
             x = xn;
-            const uint32_t na = carry ? nd : nb;
-            const uint32_t t = r - na;
-            r = r >= na ? t : t + m;
+            r = step_mod(r, carry ? nd : nb, m);
             f(i, (uint64_t)r);
         }
     } else {
@@ -332,15 +369,38 @@ __device__ __forceinline__ void packed_positions(uint64_t v, uint32_t m, uint32_
     constexpr uint64_t kMask = (1ull << kPackBits) - 1;
     uint32_t x = (uint32_t)(v & kMask);
     const uint32_t b = (uint32_t)((v >> kPackBits) & kMask), f = (uint32_t)(v >> (2 * kPackBits));
-    const uint32_t nb = m - b, bc = b >= c ? b - c : b + (m - c), nd = m - bc;
+    uint32_t nb, nd;
+    step_addends(b, m, c, nb, nd);
     pos[0] = x;
 #pragma unroll
     for (int q = 1; q < 7; ++q) {
-        const uint32_t na = (f >> (q - 1)) & 1u ? nd : nb;
-        const uint32_t t = x - na;
-        x = x >= na ? t : t + m;
+        x = step_mod(x, pick_addend(f, q - 1, nb, nd), m);
         pos[q] = x;
     }
+}
+
+// pack_residue's word and packed_positions' 7 positions of it straight from the hashes, for the
+// kernels that need both (phase 0 of the phased probes): r0, b and the six wrap flags are computed
+// once, the positions come from those registers and the word is assembled only to be stored.
+__device__ __forceinline__ uint64_t hashed_positions(uint64_t h1, uint64_t h2, const ModArg &md, uint32_t pos[7]) {
+    const uint32_t m = (uint32_t)md.m;
+    uint32_t x = mod_m31(h1, m, md.mu);
+    const uint32_t r0 = x, b = mod_m31(h2, m, md.mu);
+    uint32_t nb, nd;
+    step_addends(b, m, (uint32_t)md.c, nb, nd);
+    unsigned long long s = h1;
+    uint32_t f = 0;
+    pos[0] = x;
+#pragma unroll
+    for (int q = 1; q < 7; ++q) {
+        const bool carry = __builtin_uaddll_overflow(s, h2, &s);
+        f |= (uint32_t)carry << (q - 1);
+        x = step_mod(x, carry ? nd : nb, m);
+        pos[q] = x;
+    }
+    static_assert(2 * kPackBits == 58 && kPackBits < 32, "the flags sit in bits 26-31 of the high word");
+    const uint32_t lo = r0 | (b << kPackBits), hi = (b >> (32 - kPackBits)) | (f << (2 * kPackBits - 32));
+    return (uint64_t)hi << 32 | lo;
 }
 
 // The narrow form (m < 2^kPack6Bits): the same fields at 21 / 21 / 6 bits, 48 bits per key, in

@@ -227,8 +227,7 @@ __global__ __launch_bounds__(kPhaseBlock) void k_probe_phase0(Src src, uint64_t 
             const uint64_t i = base + (uint64_t)r * blockDim.x + threadIdx.x;
             uint64_t h1 = 0, h2 = 0;
             if (i < n) src.hash(i, h1, h2);
-            const uint64_t pw = pack_residue(h1, h2, md);  // each residue and wrap flag once
-            packed_positions(pw, (uint32_t)md.m, (uint32_t)md.c, pos[r]);
+            const uint64_t pw = hashed_positions(h1, h2, md, pos[r]);  // each residue and wrap flag once
             acc[r] = i < n ? 1u : 0u;
             if (i < n) __builtin_nontemporal_store(pw, packed + i);
         }
@@ -287,14 +286,11 @@ __global__ __launch_bounds__(kPhaseBlock) void k_probe_phase(const uint64_t *__r
             uint32_t live = (a >> (8 * r)) & 1u;
             uint32_t x = (uint32_t)(pv[r] & kMask);
             const uint32_t b = (uint32_t)((pv[r] >> kPackBits) & kMask), f = (uint32_t)(pv[r] >> (2 * kPackBits));
-            const uint32_t nb = m - b, bc = b >= c ? b - c : b + (m - c), nd = m - bc;
+            uint32_t nb, nd;
+            step_addends(b, m, c, nb, nd);
 #pragma unroll
             for (int q = 0; q < 7; ++q) {
-                if (q > 0) {
-                    const uint32_t d = (f >> (q - 1)) & 1u ? nd : nb;
-                    const uint32_t t = x - d;
-                    x = x >= d ? t : t + m;
-                }
+                if (q > 0) x = step_mod(x, pick_addend(f, q - 1, nb, nd), m);
                 const uint32_t w = x >> 5;
                 if (live && w >= lo && w < hi) live &= words[w] >> (x & 31);
             }
@@ -331,11 +327,10 @@ __global__ __launch_bounds__(kPhaseBlock) void k_probe_c0(Src src, uint64_t n, c
             const uint4 v = i < n ? src.load(i) : make_uint4(0u, 0u, 0u, 0u);
             pw = (uint64_t)v.x | (uint64_t)v.y << 32;
             packed_positions(pw, (uint32_t)md.m, (uint32_t)md.c, pos);
-        } else {  // the packed word first, the positions from it: each residue and wrap flag once
+        } else {  // each residue and wrap flag once; the packed word only for the row store
             uint64_t h1 = 0, h2 = 0;
             if (i < n) src.hash(i, h1, h2);
-            pw = pack_residue(h1, h2, md);
-            packed_positions(pw, (uint32_t)md.m, (uint32_t)md.c, pos);
+            pw = hashed_positions(h1, h2, md, pos);
         }
         uint32_t acc = i < n ? 1u : 0u;
 #pragma unroll
@@ -390,14 +385,11 @@ __global__ __launch_bounds__(kPhaseBlock) void k_probe_cp(const uint64_t *__rest
         for (int j = 0; j < G; ++j) {
             uint32_t x = (uint32_t)(pv[j] & kMask);
             const uint32_t b = (uint32_t)((pv[j] >> kPackBits) & kMask), f = (uint32_t)(pv[j] >> (2 * kPackBits));
-            const uint32_t nb = m - b, bc = b >= c ? b - c : b + (m - c), nd = m - bc;
+            uint32_t nb, nd;
+            step_addends(b, m, c, nb, nd);
 #pragma unroll
             for (int q = 0; q < 7; ++q) {
-                if (q > 0) {
-                    const uint32_t d = (f >> (q - 1)) & 1u ? nd : nb;
-                    const uint32_t t = x - d;
-                    x = x >= d ? t : t + m;
-                }
+                if (q > 0) x = step_mod(x, pick_addend(f, q - 1, nb, nd), m);
                 const uint32_t w = x >> 5;
                 if (live[j] && w >= lo && w < hi) live[j] &= words[w] >> (x & 31);
             }
@@ -434,13 +426,12 @@ __global__ __launch_bounds__(256) void k_probe_packed(const uint64_t *__restrict
             const uint64_t v = i < n ? __builtin_nontemporal_load(packed + i) : 0ull;
             uint32_t x = (uint32_t)(v & kMask);
             const uint32_t b = (uint32_t)((v >> kPackBits) & kMask), f = (uint32_t)(v >> (2 * kPackBits));
-            const uint32_t nb = m - b, bc = b >= c ? b - c : b + (m - c), nd = m - bc;
+            uint32_t nb, nd;
+            step_addends(b, m, c, nb, nd);
             pos[r][0] = x;
 #pragma unroll
             for (int q = 1; q < 7; ++q) {
-                const uint32_t na = (f >> (q - 1)) & 1u ? nd : nb;
-                const uint32_t t = x - na;
-                x = x >= na ? t : t + m;
+                x = step_mod(x, pick_addend(f, q - 1, nb, nd), m);
                 pos[r][q] = x;
             }
             acc[r] = i < n ? 1u : 0u;
