@@ -97,8 +97,8 @@ int seb_abi_version(void);
  *                     against the hashing (1, default), or by a counting sort (0)
  *   "multi_interleave" multi-filter probes with shared (m, k): bit-transposed table (0/1)
  *   "multiget_order"  registry MultiGet walks batches of >= 64K keys in key-range order (1, default:
- *                     aligned 16-B keys sorted by bucket within 2048-key chunks and read through
- *                     segment tables; 2: moved across the batch by a scatter pass) or batch order (0)
+ *                     aligned 16-B keys sorted by bucket within 4096-key super-chunks and read
+ *                     through segment tables; 2: moved across the batch by a scatter pass) or batch order (0)
  *   "multiget_piece_mib" registry MultiGet: a batch whose key-range order would need more scratch
  *                     than this (MiB, default 1024) is walked in pieces of whole 2048-key chunks
  *   "multiget_l0_group" registry MultiGet tests the L0 files that share (m, k) through one
@@ -310,6 +310,45 @@ int seb_registry_multiget_list_dev(seb_registry *reg, const seb_keys *keys, uint
  * receives the row width the registry needs now; cap < *need returns SEB_ERR_RANGE (retry). */
 int seb_registry_multiget_files(seb_registry *reg, const seb_keys *keys, uint64_t *files, uint32_t cap,
                                 uint32_t *need);
+
+/* ------------- sparse indexes + batched block locator (SSTable.Get's index step, lsm/sstable.go:210-222) ---- */
+/* Once a file's filter says "maybe", SSTable.Get bisects the file's sparse index (one entry per 4 KiB
+ * data block, lsm/sstable_builder.go:113-117) for the key and reads the block of the last entry whose
+ * key is <= the key; a key below the first entry is "not found" without a read.  The registry keeps
+ * each file's index in HBM next to its filter and answers that for every cell of a MultiGet's
+ * candidate rows, so a key batch becomes (file, block offset) pairs: all readBlock needs. */
+#define SEB_NO_BLOCK UINT64_MAX
+
+/* Host only.  Walk an encoded index block ([numEntries u32] then per entry [keySize u32][blockOffset u64]
+ * [key], little-endian) as decodeIndex does (lsm/sstable.go:168-201); *entries (nullable) = numEntries.
+ * SEB_ERR_SHORT where decodeIndex fails ("index too small": len < 4; "index truncated": an entry's
+ * 12-byte header or its key runs past the end); bytes after the last entry are ignored, as there.
+ * ONE DEPARTURE from the reference: SEB_ERR_INVALID when the keys are not non-decreasing in Go string
+ * order.  decodeIndex accepts such a block, but sort.Search's answer on it depends on its probe
+ * sequence, and SSTableBuilder never writes one; refusing it leaves the device layout free.  Equal
+ * neighbours are accepted: the answer is then the last of them, as an upper bound gives. */
+int seb_index_scan(const uint8_t *index, uint64_t index_len, uint64_t *entries);
+/* Attach the index block OpenSSTable reads (lsm/sstable.go:105-119) to a registered file; validated
+ * by the same walk (its errors), SEB_ERR_INVALID for an unknown file or a file that has one already.
+ * numEntries == 0 is a valid index: every key gets SEB_NO_BLOCK.  Released with the file's filter by
+ * seb_registry_remove / seb_registry_free. */
+int seb_registry_put_index(seb_registry *reg, uint64_t file_num, const uint8_t *index, uint64_t index_len);
+int seb_registry_index_entries(seb_registry *reg, uint64_t file_num, uint64_t *entries);
+/* cand: n x cap u16 rows exactly as seb_registry_multiget_list* writes them (slots in visiting order,
+ * 0xFFFF padding).  blocks[i*cap + j] = the BlockOffset of the last index entry of slot cand[i*cap + j]
+ * whose key is <= key i, or SEB_NO_BLOCK when there is none (blockIdx == 0), the cell is padding, or it
+ * names a free or out-of-range slot (never read out of bounds).  Every registered file must have its
+ * index: else SEB_ERR_INVALID naming the file.  cap == 0 or a null argument: SEB_ERR_INVALID; n == 0:
+ * SEB_OK, nothing launched.  The _dev form takes device pointers and is not synchronised. */
+int seb_registry_locate_dev(seb_registry *reg, const seb_keys *keys, const uint16_t *cand, uint32_t cap,
+                            uint64_t *blocks, void *stream);
+int seb_registry_locate(seb_registry *reg, const seb_keys *keys, const uint16_t *cand, uint32_t cap,
+                        uint64_t *blocks);
+/* The read plan (host keys): seb_registry_multiget_files plus blocks[i*cap + j], the block offset to
+ * read in files[i*cap + j] (SEB_NO_BLOCK: no read, and for the UINT64_MAX padding).  Same cap / *need /
+ * SEB_ERR_RANGE retry contract; lookup, locate and the slot->file mapping under one hold of the lock. */
+int seb_registry_multiget_blocks(seb_registry *reg, const seb_keys *keys, uint64_t *files, uint64_t *blocks,
+                                 uint32_t cap, uint32_t *need);
 
 /* ---------- hash-index shard routing + WAL record checksums (off the bloom path) ---- */
 /* shard[i] = FNV-1a32(key i) & ((1 << shard_bits) - 1), the reference's getShard

@@ -1883,6 +1883,10 @@ struct RegEntry {
     uint32_t k = 0;
     uint32_t *dwords = nullptr;
     std::string min_key, max_key;
+    // the file's sparse index (seb_registry_put_index): one device block holding the LocSlot arrays
+    bool has_index = false;
+    void *dindex = nullptr;
+    LocSlot loc{};
 };
 
 struct seb_registry {
@@ -1894,6 +1898,8 @@ struct seb_registry {
     DevBuf dslots, dranges;
     DevBuf dl0;                    // the L0 group's interleaved table (RegLayout::l0tab)
     DevBuf dbrange;                // per partition bucket, each disjoint level's bisection range (MgSeg::brange)
+    DevBuf dloc;                   // the locator's table: one LocSlot per slot id below max_slot
+    DevBuf dcand, dblocks;         // the host-pointer locator's candidate rows and block offsets
     bool has_brange = false;
     uint32_t nslots = 0;
     uint32_t max_cand = 0;         // longest Get walk: every L0 file + one file per non-empty level 1..4
@@ -1924,10 +1930,17 @@ extern "C" seb_registry *seb_registry_new(int device) {
 extern "C" void seb_registry_free(seb_registry *r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
-    for (auto &e : r->entries) (void)hipFree(e.dwords);
+    for (auto &e : r->entries) {
+        (void)hipFree(e.dwords);
+        if (e.dindex) (void)hipFree(e.dindex);
+    }
     r->dslots.release();
     r->dranges.release();
     r->dl0.release();
+    r->dbrange.release();
+    r->dloc.release();
+    r->dcand.release();
+    r->dblocks.release();
     if (r->ctx) seb_ctx_destroy(r->ctx);
     delete r;
 }
@@ -1983,6 +1996,7 @@ extern "C" int seb_registry_remove(seb_registry *r, uint64_t file_num) {
             HIP_OR_FAIL(hipSetDevice(r->device));
             HIP_OR_FAIL(hipDeviceSynchronize());  // no multiget may still read it
             HIP_OR_FAIL(hipFree(r->entries[i].dwords));
+            if (r->entries[i].dindex) HIP_OR_FAIL(hipFree(r->entries[i].dindex));
             r->entries.erase(r->entries.begin() + i);
             r->dirty = true;
             return SEB_OK;
@@ -2056,6 +2070,12 @@ static int sync_registry_locked(seb_registry *r) {
     uint32_t gbits = 2;
     while (gbits < grp.size()) gbits *= 2;
     int rc;
+    uint32_t max_slot = 0;
+    for (const RegEntry *e : order) max_slot = std::max(max_slot, e->slot + 1);
+    std::vector<LocSlot> loc(max_slot);  // by slot id; free slots and files without an index stay all zero
+    for (const RegEntry *e : order)
+        if (e->has_index) loc[e->slot] = e->loc;
+    if ((rc = r->dloc.reserve(sizeof(LocSlot) * (loc.size() + 1)))) return rc;
     if ((rc = r->dslots.reserve(sizeof(RegSlot) * (slots.size() + 1))) ||
         (rc = r->dranges.reserve(ranges.size() + 16)) ||
         (!grp.empty() && (rc = r->dl0.reserve(4 * l0_table_words(order[grp[0]]->m, gbits) + 16))))
@@ -2078,6 +2098,7 @@ static int sync_registry_locked(seb_registry *r) {
     }
     if (!slots.empty()) HIP_OR_FAIL(hipMemcpy(r->dslots.p, slots.data(), sizeof(RegSlot) * slots.size(), hipMemcpyHostToDevice));
     if (!ranges.empty()) HIP_OR_FAIL(hipMemcpy(r->dranges.p, ranges.data(), ranges.size(), hipMemcpyHostToDevice));
+    if (!loc.empty()) HIP_OR_FAIL(hipMemcpy(r->dloc.p, loc.data(), sizeof(LocSlot) * loc.size(), hipMemcpyHostToDevice));
     r->nslots = (uint32_t)slots.size();
     r->layout = lay;
     r->max_cand = lay.hi[0] - lay.lo[0];
@@ -2346,6 +2367,219 @@ extern "C" int seb_registry_multiget_list_dev(seb_registry *r, const seb_keys *k
                                               void *stream) {
     if (!cand && keys && keys->n) return fail(SEB_ERR_INVALID, "seb_registry_multiget_list: null output");
     return registry_multiget_dev(r, keys, nullptr, cand, cap, stream, "seb_registry_multiget_list");
+}
+
+// ---------------------------------------- sparse indexes + the batched block locator ----------
+// What SSTable.Get does with a file that passed its filter (lsm/sstable.go:210-222): bisect the
+// file's sparse index for the key and take the entry before the first greater one.  The index
+// block (decodeIndex, lsm/sstable.go:168-201: [numEntries u32] then per entry [keySize u32]
+// [blockOffset u64][key]) is parsed once into device arrays next to the file's filter words.
+
+struct IndexView {  // one walk of an encoded index block
+    std::vector<uint64_t> pre, koff, boff;
+    std::string bytes;
+};
+
+// decodeIndex's walk plus the order check; view == nullptr only validates and counts.
+static int index_walk(const uint8_t *index, uint64_t len, uint64_t *entries, IndexView *view, const char *who) {
+    if (len && !index) return fail(SEB_ERR_INVALID, "%s: null index", who);
+    if (len < 4) return fail(SEB_ERR_SHORT, "%s: index too small (%llu bytes)", who, (unsigned long long)len);
+    uint32_t num;
+    memcpy(&num, index, 4);
+    uint64_t at = 4;
+    const uint8_t *prev = nullptr;
+    uint64_t prev_len = 0;
+    if (view) view->koff.push_back(0);
+    for (uint32_t e = 0; e < num; ++e) {
+        if (len - at < 12) return fail(SEB_ERR_SHORT, "%s: index truncated in the header of entry %u", who, e);
+        uint32_t ks;
+        uint64_t bo;
+        memcpy(&ks, index + at, 4);
+        memcpy(&bo, index + at + 4, 8);
+        at += 12;
+        if (len - at < ks) return fail(SEB_ERR_SHORT, "%s: index truncated in the key of entry %u", who, e);
+        const uint8_t *key = index + at;
+        if (prev) {  // Go string order: bytewise, a proper prefix first
+            const int c = memcmp(prev, key, (size_t)std::min<uint64_t>(prev_len, ks));
+            if (c > 0 || (c == 0 && prev_len > ks))
+                return fail(SEB_ERR_INVALID, "%s: index keys decrease at entry %u", who, e);
+        }
+        if (view) {
+            uint64_t be[2];
+            be_prefix(std::string((const char *)key, std::min<uint32_t>(ks, 16)), be);
+            view->pre.push_back(be[0]);
+            view->pre.push_back(be[1]);
+            view->boff.push_back(bo);
+            view->bytes.append((const char *)key, ks);
+            view->koff.push_back(view->bytes.size());
+        }
+        prev = key;
+        prev_len = ks;
+        at += ks;
+    }
+    if (entries) *entries = num;
+    return SEB_OK;
+}
+
+extern "C" int seb_index_scan(const uint8_t *index, uint64_t index_len, uint64_t *entries) {
+    if (entries) *entries = 0;
+    return index_walk(index, index_len, entries, nullptr, "seb_index_scan");
+}
+
+extern "C" int seb_registry_put_index(seb_registry *r, uint64_t file_num, const uint8_t *index, uint64_t index_len) {
+    const char *who = "seb_registry_put_index";
+    if (!r) return fail(SEB_ERR_INVALID, "%s: null registry", who);
+    IndexView v;
+    uint64_t n = 0;
+    int rc;
+    if ((rc = index_walk(index, index_len, &n, &v, who))) return rc;
+    std::lock_guard<std::mutex> g(r->mu);
+    RegEntry *e = nullptr;
+    for (auto &x : r->entries)
+        if (x.file_num == file_num) e = &x;
+    if (!e) return fail(SEB_ERR_INVALID, "%s: file %llu not registered", who, (unsigned long long)file_num);
+    if (e->has_index) return fail(SEB_ERR_INVALID, "%s: file %llu already has an index", who, (unsigned long long)file_num);
+    LocSlot loc{};
+    void *d = nullptr;
+    if (n) {  // one block: pre (16 B per entry) | boff | koff (n + 1) | bytes
+        DeviceGuard dg;
+        if ((rc = dg.set(r->device))) return rc;
+        const uint64_t pre_b = 16 * n, boff_b = 8 * n, koff_b = 8 * (n + 1);
+        hipError_t a = hipMalloc(&d, pre_b + boff_b + koff_b + v.bytes.size() + 16);
+        if (a != hipSuccess) return (void)hipGetLastError(), fail(SEB_ERR_NOMEM, "%s: hipMalloc: %s", who, hipGetErrorString(a));
+        uint8_t *p = (uint8_t *)d;
+        hipError_t c = hipMemcpy(p, v.pre.data(), pre_b, hipMemcpyHostToDevice);
+        if (c == hipSuccess) c = hipMemcpy(p + pre_b, v.boff.data(), boff_b, hipMemcpyHostToDevice);
+        if (c == hipSuccess) c = hipMemcpy(p + pre_b + boff_b, v.koff.data(), koff_b, hipMemcpyHostToDevice);
+        if (c == hipSuccess && !v.bytes.empty())
+            c = hipMemcpy(p + pre_b + boff_b + koff_b, v.bytes.data(), v.bytes.size(), hipMemcpyHostToDevice);
+        if (c != hipSuccess) {
+            (void)hipFree(d);
+            (void)hipGetLastError();
+            return fail(hip_status(c), "%s: hipMemcpy: %s", who, hipGetErrorString(c));
+        }
+        loc.pre = (const uint64_t *)p;
+        loc.boff = (const uint64_t *)(p + pre_b);
+        loc.koff = (const uint64_t *)(p + pre_b + boff_b);
+        loc.bytes = p + pre_b + boff_b + koff_b;
+        loc.n = (uint32_t)n;
+    }
+    e->has_index = true;
+    e->dindex = d;
+    e->loc = loc;
+    r->dirty = true;
+    return SEB_OK;
+}
+
+extern "C" int seb_registry_index_entries(seb_registry *r, uint64_t file_num, uint64_t *entries) {
+    const char *who = "seb_registry_index_entries";
+    if (!r || !entries) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    std::lock_guard<std::mutex> g(r->mu);
+    for (auto &e : r->entries)
+        if (e.file_num == file_num) {
+            if (!e.has_index) return fail(SEB_ERR_INVALID, "%s: file %llu has no index", who, (unsigned long long)file_num);
+            *entries = e.loc.n;
+            return SEB_OK;
+        }
+    return fail(SEB_ERR_INVALID, "%s: file %llu not registered", who, (unsigned long long)file_num);
+}
+
+// r->mu held: every registered file must have its index before cells may name it.
+static int check_indexes_locked(const seb_registry *r, const char *who) {
+    for (auto &e : r->entries)
+        if (!e.has_index)
+            return fail(SEB_ERR_INVALID, "%s: file %llu has no index (seb_registry_put_index)", who,
+                        (unsigned long long)e.file_num);
+    return SEB_OK;
+}
+
+extern "C" int seb_registry_locate_dev(seb_registry *r, const seb_keys *keys, const uint16_t *cand, uint32_t cap,
+                                       uint64_t *blocks, void *stream) {
+    const char *who = "seb_registry_locate";
+    enter();
+    int rc;
+    if (!r || !cand || !blocks) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if (cap == 0) return fail(SEB_ERR_INVALID, "%s: cap 0", who);
+    if ((rc = check_keys(keys, who))) return rc;
+    DeviceGuard dg;
+    if ((rc = dg.set(r->device))) return rc;
+    std::lock_guard<std::mutex> g(r->mu);
+    if ((rc = sync_registry_locked(r)) || (rc = check_indexes_locked(r, who))) return rc;
+    if (keys->n == 0) return SEB_OK;
+    HIP_OR_FAIL(launch_locate(key_batch(keys), cand, cap, (const LocSlot *)r->dloc.p, r->max_slot, blocks,
+                              (hipStream_t)stream));
+    return SEB_OK;
+}
+
+// Host keys through the registry's own context, a chunk at a time on its compute stream; r->mu held,
+// registry synced, indexes checked.  cand_in != null: locate those rows.  Else the MultiGet's own rows
+// are located and copied to cand_out.
+static int registry_locate_host_locked(seb_registry *r, const seb_keys *kb, const uint16_t *cand_in, uint16_t *cand_out,
+                                       uint32_t cap, uint64_t *blocks) {
+    WsCall ws_call;
+    int rc;
+    if (!r->ctx && (rc = seb_ctx_create(r->device, &r->ctx))) return rc;
+    seb_ctx *c = r->ctx;
+    std::lock_guard<std::mutex> g2(c->mu);
+    HIP_OR_FAIL(hipSetDevice(c->device));
+    std::vector<Chunk> chunks;
+    plan_chunks(kb, c->chunk_bytes, chunks);
+    for (const Chunk &ch : chunks) {
+        KeyBatch dk{};
+        if ((rc = stage_chunk(c, kb, ch, 0, &dk, true))) return rc;
+        const uint64_t cells = dk.n * (uint64_t)cap;
+        if ((rc = r->dcand.reserve(cells * 2)) || (rc = r->dblocks.reserve(cells * 8))) return rc;
+        uint16_t *dc = (uint16_t *)r->dcand.p;
+        if (cand_in) {
+            HIP_OR_FAIL(hipMemcpyAsync(dc, cand_in + ch.i0 * cap, cells * 2, hipMemcpyHostToDevice, c->s_comp));
+        } else {
+            if ((rc = multiget_launch(r, dk, nullptr, dc, cap, c->s_comp))) return rc;
+            HIP_OR_FAIL(hipMemcpyAsync(cand_out + ch.i0 * cap, dc, cells * 2, hipMemcpyDeviceToHost, c->s_comp));
+        }
+        HIP_OR_FAIL(launch_locate(dk, dc, cap, (const LocSlot *)r->dloc.p, r->max_slot, (uint64_t *)r->dblocks.p,
+                                  c->s_comp));
+        HIP_OR_FAIL(hipMemcpyAsync(blocks + ch.i0 * cap, r->dblocks.p, cells * 8, hipMemcpyDeviceToHost, c->s_comp));
+        HIP_OR_FAIL(hipStreamSynchronize(c->s_comp));  // the staging buffers are reused by the next chunk
+    }
+    return SEB_OK;
+}
+
+extern "C" int seb_registry_locate(seb_registry *r, const seb_keys *kb, const uint16_t *cand, uint32_t cap,
+                                   uint64_t *blocks) {
+    const char *who = "seb_registry_locate";
+    int rc;
+    if (!r || !cand || !blocks) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if (cap == 0) return fail(SEB_ERR_INVALID, "%s: cap 0", who);
+    if ((rc = check_keys(kb, who)) || (rc = validate_offsets(kb, who))) return rc;
+    std::lock_guard<std::mutex> g(r->mu);
+    if ((rc = sync_registry_locked(r)) || (rc = check_indexes_locked(r, who))) return rc;
+    if (kb->n == 0) return SEB_OK;
+    return registry_locate_host_locked(r, kb, cand, nullptr, cap, blocks);
+}
+
+// seb_registry_multiget_files plus each candidate's block offset: lookup, locate and the slot->file
+// mapping under ONE hold of the registry lock.
+extern "C" int seb_registry_multiget_blocks(seb_registry *r, const seb_keys *kb, uint64_t *files, uint64_t *blocks,
+                                            uint32_t cap, uint32_t *need) {
+    const char *who = "seb_registry_multiget_blocks";
+    int rc;
+    if (!r) return fail(SEB_ERR_INVALID, "%s: null registry", who);
+    if ((rc = check_keys(kb, who)) || (rc = validate_offsets(kb, who))) return rc;
+    if ((!files || !blocks) && kb->n) return fail(SEB_ERR_INVALID, "%s: null output", who);
+    std::lock_guard<std::mutex> g(r->mu);
+    if ((rc = sync_registry_locked(r))) return rc;
+    const uint32_t want = std::max<uint32_t>(r->max_cand, 1);
+    if (need) *need = want;
+    if (cap < want)
+        return fail(SEB_ERR_RANGE, "%s: cap %u < %u candidates a key can have now; retry with *need", who, cap, want);
+    if ((rc = check_indexes_locked(r, who))) return rc;
+    if (kb->n == 0) return SEB_OK;
+    std::vector<uint16_t> cand(kb->n * (uint64_t)cap);
+    if ((rc = registry_locate_host_locked(r, kb, nullptr, cand.data(), cap, blocks))) return rc;
+    std::vector<uint64_t> by_slot(kRegMaxFiles, UINT64_MAX);
+    for (auto &e : r->entries) by_slot[e.slot] = e.file_num;
+    for (uint64_t i = 0; i < cand.size(); ++i) files[i] = cand[i] == 0xFFFF ? UINT64_MAX : by_slot[cand[i]];
+    return SEB_OK;
 }
 
 // ------------------------------------------------ shard routing + WAL checksums (§8(f) row 4)

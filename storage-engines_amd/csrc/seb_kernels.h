@@ -133,6 +133,22 @@ hipError_t launch_multiget_order(const KeyBatch &kb, const RegSlot *slots, uint3
                                  const uint8_t *ranges, void *ws, MgOrder *mo, hipStream_t s);
 hipError_t launch_multiget_unpermute(const MgOrder &mo, void *out, uint64_t answer_bytes, hipStream_t s);
 
+// seb_locate.hip: a registered file's sparse index (lsm/sstable.go:168-201) in HBM as a structure of
+// arrays, one table entry per registry slot id (a free slot, or a file without an index yet: all zero).
+struct LocSlot {
+    const uint64_t *pre;   // entry e: pre[2e], pre[2e+1] = its key's first 16 bytes, zero padded, big-endian (16-B aligned)
+    const uint64_t *koff;  // n + 1 offsets into bytes: key e = bytes[koff[e], koff[e+1]), so its length too
+    const uint64_t *boff;  // entry e's BlockOffset
+    const uint8_t *bytes;  // the keys' bytes, read only where 16-byte prefixes tie
+    uint32_t n;            // entries
+    uint32_t pad;
+};
+constexpr uint64_t kNoBlock = ~0ull;  // SEB_NO_BLOCK
+// blocks[i * cap + j] = the block offset SSTable.Get would read for key i in the file of slot
+// cand[i * cap + j] (lsm/sstable.go:210-222), kNoBlock for none; slots >= ntab have no index.
+hipError_t launch_locate(const KeyBatch &kb, const uint16_t *cand, uint32_t cap, const LocSlot *tab, uint32_t ntab,
+                         uint64_t *blocks, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

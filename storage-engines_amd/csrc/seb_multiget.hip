@@ -18,43 +18,11 @@
 
 #include "seb_device.h"
 #include "seb_kernels.h"
+#include "seb_keycmp.h"
 
 namespace seb {
 
 constexpr uint32_t kMaxSlots = 64;  // slot tables up to this size are staged in LDS
-
-__device__ __forceinline__ uint64_t be64(const uint8_t *p, uint32_t len) {  // first min(len,8) bytes, big-endian
-    uint64_t v = 0;
-    for (uint32_t i = 0; i < 8; ++i) v = (v << 8) | (i < len ? p[i] : 0u);
-    return v;
-}
-
-// The key's first 16 bytes as two big-endian words: one 16-B load for aligned fixed-width 16-B
-// keys (the batch layout of the benchmarks), else byte loads.
-__device__ __forceinline__ void key_prefix(const KeyBatch &kb, const uint8_t *key, uint32_t klen, uint64_t &k0,
-                                           uint64_t &k1) {
-    if (!kb.offsets && kb.stride == 16 && ((uintptr_t)kb.data & 15) == 0) {
-        const uint4 v = *(const uint4 *)key;
-        k0 = __builtin_bswap64((uint64_t)v.x | ((uint64_t)v.y << 32));
-        k1 = __builtin_bswap64((uint64_t)v.z | ((uint64_t)v.w << 32));
-    } else {
-        k0 = be64(key, klen);
-        k1 = klen > 8 ? be64(key + 8, klen - 8) : 0ull;
-    }
-}
-
-// Go bytewise compare of key (k0,k1 = its first 16 bytes big-endian) vs a stored range key.
-__device__ __forceinline__ int cmp_key(const uint8_t *key, uint32_t klen, uint64_t k0, uint64_t k1,
-                                       const uint64_t be[2], const uint8_t *bytes, uint32_t blen) {
-    if (k0 != be[0]) return k0 < be[0] ? -1 : 1;
-    if (k1 != be[1]) return k1 < be[1] ? -1 : 1;
-    // equal zero-padded 16-byte prefixes: the shorter key is a prefix of the other unless both
-    // run past 16 bytes, where the tail bytes (in HBM) decide
-    const uint32_t n = klen < blen ? klen : blen;
-    for (uint32_t i = 16; i < n; ++i)
-        if (key[i] != bytes[i]) return key[i] < bytes[i] ? -1 : 1;
-    return (int)klen - (int)blen;
-}
 
 // A filter word from global memory.  The words pointers come out of RegSlot / RegLayout structs, so
 // the compiler cannot tell their address space and would issue flat loads (which also count against

@@ -4,6 +4,8 @@
 //	OpenSSTable (lsm/sstable.go:121-129)        -> reg.Put(fileNum, level, bloomBlock, minKey, maxKey)
 //	compaction removes inputs (compaction.go:335-343) -> reg.Remove(fileNum)
 //	LSM.Get's walk + MayContain (lsm/lsm.go:168-198) -> reg.Candidates(keys)
+//	OpenSSTable reads indexData (lsm/sstable.go:105-119)   -> reg.PutIndex(fileNum, indexData)
+//	SSTable.Get's index bisection (lsm/sstable.go:210-222) -> reg.MultiGetBlocks(keys)
 //
 // Not compiled in this repository's pipeline (no Go toolchain in the image); the C ABI it calls is
 // tested through the Python binding (tests/test_gpu_parity.py, test_registry_*).
@@ -120,6 +122,73 @@ func (r *FilterRegistry) Candidates(keys []string) [][]uint64 {
 				break
 			}
 			out[i] = append(out[i], f)
+		}
+	}
+	return out
+}
+
+// PutIndex attaches a registered file's encoded index block: the indexData OpenSSTable hands to
+// decodeIndex (lsm/sstable.go:105-119).  It is kept in HBM beside the file's filter and freed by Remove.
+func (r *FilterRegistry) PutIndex(fileNum uint64, indexData []byte) {
+	if C.seb_registry_put_index(r.h, C.uint64_t(fileNum), bytesPtr(indexData), C.uint64_t(len(indexData))) != 0 {
+		regPanic("PutIndex")
+	}
+	runtime.KeepAlive(indexData)
+}
+
+// BlockRead is one read of a MultiGet's plan: readBlock(Offset) in SSTable File.
+type BlockRead struct {
+	File   uint64
+	Offset uint64
+}
+
+// MultiGetBlocks is Candidates plus SSTable.Get's index step (lsm/sstable.go:210-222): per key, in
+// Get's visiting order, the files whose filter may contain it and the offset of the one data block
+// to read in each.  A candidate file whose first index key sorts after the key is left out, as Get
+// returns "not found" for it without a read.  Every registered file needs PutIndex first.
+func (r *FilterRegistry) MultiGetBlocks(keys []string) [][]BlockRead {
+	out := make([][]BlockRead, len(keys))
+	if len(keys) == 0 {
+		return out
+	}
+	data, offs := packKeys(keys)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&data[0])
+	pin.Pin(&offs[0])
+	ks := (*C.seb_keys)(C.malloc(C.size_t(unsafe.Sizeof(C.seb_keys{}))))
+	defer C.free(unsafe.Pointer(ks))
+	*ks = C.seb_keys{data: (*C.uint8_t)(unsafe.Pointer(&data[0])), offsets: (*C.uint64_t)(unsafe.Pointer(&offs[0])),
+		n: C.uint64_t(len(keys))}
+	capRow := C.uint32_t(r.capHint.Load())
+	if capRow == 0 {
+		capRow = 1
+	}
+	var files, blocks []uint64
+	for { // SEB_ERR_RANGE: the registry grew since the last call; retry with the width it reports
+		files = make([]uint64, len(keys)*int(capRow))
+		blocks = make([]uint64, len(keys)*int(capRow))
+		var need C.uint32_t
+		rc := C.seb_registry_multiget_blocks(r.h, ks, (*C.uint64_t)(unsafe.Pointer(&files[0])),
+			(*C.uint64_t)(unsafe.Pointer(&blocks[0])), capRow, &need)
+		if rc == C.int(C.SEB_ERR_RANGE) && need > capRow {
+			capRow = need
+			continue
+		}
+		if rc != 0 {
+			regPanic("MultiGetBlocks")
+		}
+		r.capHint.Store(uint32(capRow))
+		break
+	}
+	runtime.KeepAlive(data)
+	runtime.KeepAlive(offs)
+	w := int(capRow)
+	for i := range keys {
+		for j := i * w; j < (i+1)*w && files[j] != ^uint64(0); j++ {
+			if blocks[j] != ^uint64(0) { // SEB_NO_BLOCK: blockIdx == 0, nothing to read
+				out[i] = append(out[i], BlockRead{File: files[j], Offset: blocks[j]})
+			}
 		}
 	}
 	return out

@@ -110,6 +110,12 @@ _SIGS = {
     "seb_registry_multiget_list": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32]),
     "seb_registry_multiget_list_dev": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp]),
     "seb_registry_multiget_files": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, C.POINTER(_u32)]),
+    "seb_index_scan": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "seb_registry_put_index": (_i, [_vp, _u64, _vp, _u64]),
+    "seb_registry_index_entries": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "seb_registry_locate_dev": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp, _vp]),
+    "seb_registry_locate": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp]),
+    "seb_registry_multiget_blocks": (_i, [_vp, C.POINTER(seb_keys), _vp, _vp, _u32, C.POINTER(_u32)]),
     "seb_workspace_bytes": (_u64, []),
     "seb_dev_or_slices": (_i, [_vp, _u32, _u64, _vp, _vp]),
     "seb_workspace_release": (_i, []),
@@ -132,6 +138,7 @@ _SIGS = {
 }
 
 WAL_CRC, WAL_SEAL, WAL_VERIFY = 0, 1, 2
+NO_BLOCK = 2**64 - 1  # SEB_NO_BLOCK: no index entry <= the key, a padded cell, or a slot without a file
 
 
 def build_library() -> str:
@@ -437,6 +444,56 @@ class Registry:
     def multiget_dev(self, keys: "seb_keys", out, stream=None) -> None:
         check(lib().seb_registry_multiget_dev(self._h, C.byref(keys), out.data_ptr(), _stream(stream)))
 
+    def put_index(self, file_num: int, index_block: bytes) -> None:
+        """Attach a registered file's encoded index block (the bytes OpenSSTable hands decodeIndex,
+        lsm/sstable.go:105-119)."""
+        check(lib().seb_registry_put_index(self._h, file_num, index_block, len(index_block)))
+
+    def index_entries(self, file_num: int) -> int:
+        n = _u64()
+        check(lib().seb_registry_index_entries(self._h, file_num, C.byref(n)))
+        return n.value
+
+    def locate(self, keys, cand: np.ndarray) -> np.ndarray:
+        """Per cell of multiget_list's (n, cap) u16 rows, the offset of the data block SSTable.Get
+        would read in that file (lsm/sstable.go:210-222), NO_BLOCK for none: an (n, cap) u64 array."""
+        kb = as_keys(keys)
+        cand = np.ascontiguousarray(cand, dtype=np.uint16)
+        if cand.ndim != 2 or cand.shape[0] != kb.n:
+            raise ValueError("cand must be an (n, cap) array of u16 slots")
+        cap = cand.shape[1]
+        src = cand if cand.size else np.zeros(1, np.uint16)
+        out = np.zeros((max(kb.n, 1), max(cap, 1)), dtype=np.uint64)
+        check(lib().seb_registry_locate(self._h, kb.ref, src.ctypes.data, cap, out.ctypes.data))
+        return out[: kb.n, :cap]
+
+    def locate_dev(self, keys: "seb_keys", cand, blocks, cap: int, stream=None) -> None:
+        """Device form: cand (n * cap u16) and blocks (n * cap u64) are device tensors; not synchronised."""
+        cells = keys.n * cap
+        if cand.numel() * cand.element_size() < 2 * cells:
+            raise ValueError(f"cand holds {cand.numel() * cand.element_size()} bytes, n * cap u16 cells need {2 * cells}")
+        if blocks.numel() * blocks.element_size() < 8 * cells:
+            raise ValueError(f"blocks holds {blocks.numel() * blocks.element_size()} bytes, n * cap u64 cells need "
+                             f"{8 * cells}")
+        check(lib().seb_registry_locate_dev(self._h, C.byref(keys), cand.data_ptr(), cap, blocks.data_ptr(),
+                                            _stream(stream)))
+
+    def multiget_blocks(self, keys, cap: int = 1) -> tuple[np.ndarray, np.ndarray]:
+        """The read plan: multiget_files' (n, cap) file numbers and, parallel to them, the block
+        offset to read in each (NO_BLOCK: none), from one atomic registry call."""
+        kb = as_keys(keys)
+        need = _u32()
+        while True:
+            files = np.zeros((max(kb.n, 1), cap), dtype=np.uint64)
+            blocks = np.zeros((max(kb.n, 1), cap), dtype=np.uint64)
+            rc = lib().seb_registry_multiget_blocks(self._h, kb.ref, files.ctypes.data, blocks.ctypes.data, cap,
+                                                    C.byref(need))
+            if rc == -4 and need.value > cap:
+                cap = need.value
+                continue
+            check(rc)
+            return files[: kb.n], blocks[: kb.n]
+
 
 # ------------------------------------------------- device-resident API (torch tensors) ----
 
@@ -560,14 +617,22 @@ def pack6_supported(m: int, k: int) -> bool:
     return k == 7 and 0 < m < (1 << PACK6_BITS)
 
 
+def _check_packed6(packed6, n: int) -> None:
+    have = packed6.numel() * packed6.element_size()
+    if have < packed6_bytes(n):  # whole 64-key blocks: 6 * n bytes is short unless n % 64 == 0
+        raise ValueError(f"packed6 holds {have} bytes, {n} keys need packed6_bytes(n) = {packed6_bytes(n)}")
+
+
 def dev_pack_residues6(keys: seb_keys, m: int, k: int, packed6, stream=None) -> None:
     """6-byte packed residues per key in 64-key blocks (k == 7, m < 2^21): a quarter fewer bytes
     than dev_pack_residues for the batch a compaction-sized filter set shares."""
+    _check_packed6(packed6, keys.n)
     check(lib().seb_dev_pack_residues6(C.byref(keys), m, k, packed6.data_ptr(), _stream(stream)))
 
 
 def dev_probe_multi_packed6(packed6, n: int, filters: list[tuple[object, int, int]], mask, stream=None) -> None:
     """dev_probe_multi over 6-byte packed residues (filters of one (m, k); k == 7, m < 2^21)."""
+    _check_packed6(packed6, n)
     refs = (seb_filter_ref * len(filters))(*[seb_filter_ref(w.data_ptr(), m, k, 0) for w, m, k in filters])
     check(lib().seb_dev_probe_multi_packed6(packed6.data_ptr(), n, refs, len(filters), mask.data_ptr(),
                                             mask.element_size(), _stream(stream)))
@@ -629,6 +694,14 @@ def dev_wal_crc(data, rec_off, mode: int = WAL_CRC, crc=None, ok=None, stream=No
     VERIFY sets ok[i] (framing + stored CRC, lsm/wal.go:123-133)."""
     check(lib().seb_dev_wal_crc(data.data_ptr(), rec_off.data_ptr(), rec_off.numel() - 1, mode, _ptr(crc), _ptr(ok),
                                 _stream(stream)))
+
+
+def index_scan(block: bytes) -> int:
+    """decodeIndex's walk (lsm/sstable.go:168-201) on the host: the entry count, or SebError (SHORT:
+    too small / truncated; INVALID: keys not non-decreasing)."""
+    n = _u64(0)
+    check(lib().seb_index_scan(block, len(block), C.byref(n)))
+    return n.value
 
 
 def wal_scan(image: bytes | np.ndarray) -> tuple[np.ndarray, int]:

@@ -20,7 +20,7 @@ while [ $# -gt 0 ]; do
 done
 C=$SRC/storage-engines_amd/csrc
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function ${FLAGS[*]}"
-for f in seb_kernels seb_bucket seb_varlen seb_multiget seb_codec; do
+for f in $(cd $C && ls *.hip | sed "s/\.hip$//"); do
   /opt/rocm/bin/hipcc $FL -c $C/$f.hip -o $OUT/obj/$f.o &
 done
 /opt/rocm/bin/hipcc $FL -c $C/seb_host.cpp -o $OUT/obj/seb_host.o &

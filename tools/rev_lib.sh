@@ -11,7 +11,7 @@ rm -rf "$SRC" && mkdir -p "$OUT/obj" "$SRC/storage-engines_amd/csrc" "$SRC/inclu
 (cd "$ROOT" && git archive "$REV" storage-engines_amd/csrc include) | tar -x -C "$SRC"
 C=$SRC/storage-engines_amd/csrc
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
-for f in seb_kernels seb_bucket seb_varlen seb_multiget seb_codec; do
+for f in $(cd $C && ls *.hip | sed "s/\.hip$//"); do
   /opt/rocm/bin/hipcc $FL -c $C/$f.hip -o $OUT/obj/$f.o &
 done
 /opt/rocm/bin/hipcc $FL -c $C/seb_host.cpp -o $OUT/obj/seb_host.o &
