@@ -350,6 +350,77 @@ int seb_registry_locate(seb_registry *reg, const seb_keys *keys, const uint16_t 
 int seb_registry_multiget_blocks(seb_registry *reg, const seb_keys *keys, uint64_t *files, uint64_t *blocks,
                                  uint32_t cap, uint32_t *need);
 
+/* ------------- batched data-block search: SSTable.Get's last step + LSM.Get's decision over a key's files ---- */
+/* With the block to read known per cell, SSTable.Get reads it and walks it for the key (searchBlock,
+ * lsm/sstable.go:242-290); LSM.Get takes the first file, in visiting order, that answers "found" or fails
+ * (lsm/lsm.go:174-197).  The caller reads the blocks (the library reads no file) into a block pool; this
+ * group searches every cell's block for its key and resolves each key's row of cells.
+ *
+ * A block image is [numEntries u32] then per entry [keySize u32][valueSize u32][deleted u8][key][value],
+ * little-endian, at most SEB_BLOCK_BYTES bytes (readBlock returns block[:n], n <= 4096).  The walk, bit-exact:
+ * fewer than 4 bytes: not found.  For each of numEntries entries: a 9-byte header or a key + value that runs
+ * past the image is the error "block truncated" (sizes added in 64 bits, as Go's int does; nothing wraps); an
+ * entry equal to the key answers (deleted == 1 exactly: a tombstone; any other byte: the value); an entry
+ * greater than the key in Go string order ends the walk with "not found".  The first entry in walk order that
+ * does one of the three decides; nothing checks that the block is sorted, so an unsorted block, duplicate
+ * keys and a wrong numEntries are answered by the walk (an equal entry behind a greater one is never reached,
+ * the first duplicate wins, an overstated count walks into the zero padding as empty-key entries).
+ *
+ * A TOMBSTONE INSIDE AN SSTABLE DOES NOT END LSM.Get: sst.Get returns found == false for it
+ * (sstable.go:273-275), so lsm.go:175-181,187-196 go on to the next, older file, and a value there is
+ * returned.  seb_dev_resolve_rows does the same; the cell status tells a caller that wants otherwise.
+ *
+ * Block pool: caller-owned memory of num_blocks slots of SEB_BLOCK_BYTES bytes; block b is
+ * pool[b * 4096, b * 4096 + blen[b]) with blen[b] <= 4096 (a larger blen is read as 4096); the base must be
+ * 16-byte aligned.  The pool may persist across calls (a device block cache); the library never allocates or
+ * copies it.  A cell names its block by id: bid[i * cap + j], or SEB_NO_BLOCK_ID for "no read".
+ * A cell's result is one u32, status << 28 | voff << 13 | vlen: voff = the value's byte offset inside the
+ * block (0..4096), vlen its size (<= 4083), both 0 unless the status is SEB_CELL_FOUND. */
+#define SEB_BLOCK_BYTES 4096u
+#define SEB_NO_BLOCK_ID UINT32_MAX
+enum seb_cell_status {
+    SEB_CELL_NONE = 0,      /* the id is SEB_NO_BLOCK_ID or >= num_blocks: nothing was read */
+    SEB_CELL_MISS = 1,      /* not found */
+    SEB_CELL_FOUND = 2,     /* the value is block[voff, voff + vlen) */
+    SEB_CELL_TOMBSTONE = 3, /* the key's entry is deleted */
+    SEB_CELL_TRUNC = 4,     /* searchBlock's error "block truncated" */
+};
+#define SEB_CELL(status, voff, vlen) ((uint32_t)(status) << 28 | (uint32_t)(voff) << 13 | (uint32_t)(vlen))
+#define SEB_CELL_STATUS(cell) ((uint32_t)(cell) >> 28)
+#define SEB_CELL_VOFF(cell) (((uint32_t)(cell) >> 13) & 0x1FFFu)
+#define SEB_CELL_VLEN(cell) ((uint32_t)(cell) & 0x1FFFu)
+enum seb_get_status { SEB_GET_MISS = 0, SEB_GET_FOUND = 1, SEB_GET_ERROR = 2 };
+
+/* Host only: the walk above for one block image and one key.  len > 4096 or a null pointer with a non-zero
+ * length: SEB_ERR_INVALID.  "block truncated" is a cell status, not an error code. */
+int seb_block_search(const uint8_t *block, uint64_t len, const uint8_t *key, uint64_t key_len, uint32_t *cell);
+/* Device pointers, not synchronised.  cells[c] for each of the n * cap cells = seb_block_search of pool block
+ * bid[c] and key c / cap (SEB_CELL_NONE for an id that names no block; nothing is read for it).  Keys in every
+ * seb_keys layout.  n == 0: SEB_OK, nothing launched; cap == 0, a null argument or a pool that is not 16-byte
+ * aligned: SEB_ERR_INVALID.  Nothing past the n * cap cells is written. */
+int seb_dev_search_blocks(const seb_keys *keys, const uint32_t *bid, uint32_t cap, const uint8_t *pool,
+                          const uint16_t *blen, uint32_t num_blocks, uint32_t *cells, void *stream);
+/* Device pointers, not synchronised.  Per key, the deciding cell is the first of its row's cap cells whose
+ * status is SEB_CELL_FOUND or SEB_CELL_TRUNC: status[i] = SEB_GET_FOUND / SEB_GET_ERROR, or SEB_GET_MISS when
+ * there is none (tombstones do not decide, see above); col[i] = its column, 0xFFFF for none;
+ * vloc[i] = bid * 4096 + voff, the value's byte offset in the pool, and vlen[i] its size, both 0 unless
+ * found.  col, vloc and vlen may be null. */
+int seb_dev_resolve_rows(const uint32_t *cells, const uint32_t *bid, uint64_t n, uint32_t cap, uint8_t *status,
+                         uint16_t *col, uint64_t *vloc, uint32_t *vlen, void *stream);
+/* The host-buffer form on a context: keys, bid (n * cap), pool (num_blocks * 4096 bytes) and blen in host
+ * memory; H2D, both kernels, D2H; synchronous.  status is required; col, vloc, vlen and cells (the n * cap cell
+ * results) may be null. */
+int seb_search_blocks(seb_ctx *ctx, const seb_keys *keys, const uint32_t *bid, uint32_t cap, const uint8_t *pool,
+                      const uint16_t *blen, uint32_t num_blocks, uint8_t *status, uint16_t *col, uint64_t *vloc,
+                      uint32_t *vlen, uint32_t *cells);
+/* Host only: seb_registry_multiget_blocks' parallel (file, block offset) arrays into the read list.  Each
+ * distinct pair once, in first-appearance order, in uniq_files / uniq_blocks (uniq_cap entries each), and
+ * bid[c] = its position for every cell; a cell whose block is SEB_NO_BLOCK gets SEB_NO_BLOCK_ID.  The same
+ * offset in two files is two blocks.  *num_uniq = the number of distinct pairs; uniq_cap below it:
+ * SEB_ERR_RANGE (nothing in bid or uniq_* is then meaningful; retry with *num_uniq). */
+int seb_blocks_dedup(const uint64_t *files, const uint64_t *blocks, uint64_t cells, uint32_t *bid,
+                     uint64_t *uniq_files, uint64_t *uniq_blocks, uint64_t uniq_cap, uint64_t *num_uniq);
+
 /* ---------- hash-index shard routing + WAL record checksums (off the bloom path) ---- */
 /* shard[i] = FNV-1a32(key i) & ((1 << shard_bits) - 1), the reference's getShard
  * (hashindex/shard.go:47-52; 256 shards = shard_bits 8).  hash[i] (nullable) = the full FNV-1a32.

@@ -21,6 +21,10 @@
 
 namespace seb {
 int params(int64_t n, double p, uint64_t *m_out, uint32_t *k_out);
+// seb_block.cpp
+int block_search(const uint8_t *block, uint64_t len, const uint8_t *key, uint64_t key_len, uint32_t *cell);
+int blocks_dedup(const uint64_t *files, const uint64_t *blocks, uint64_t cells, uint32_t *bid, uint64_t *uniq_files,
+                 uint64_t *uniq_blocks, uint64_t uniq_cap, uint64_t *num_uniq);
 }
 
 using namespace seb;
@@ -1003,6 +1007,7 @@ struct seb_ctx {
     hipStream_t s_h2d = nullptr, s_comp = nullptr, s_d2h = nullptr;
     hipEvent_t ev_h2d[2] = {}, ev_comp[2] = {}, ev_d2h[2] = {};
     DevBuf keys[2], offs[2], out[2], words, filt, ws;
+    DevBuf sb_bid, sb_pool, sb_blen, sb_cells, sb_out;  // seb_search_blocks: its inputs and outputs on the device
     PinBuf hkeys, hbits;  // small filter builds: keys in, bits out, read and written by the kernels
     uint64_t chunk_bytes = 64ull << 20;
     std::vector<uint64_t> off_tmp[2];
@@ -1049,6 +1054,7 @@ extern "C" void seb_ctx_destroy(seb_ctx *c) {
     c->words.release();
     c->filt.release();
     c->ws.release();
+    for (DevBuf *b : {&c->sb_bid, &c->sb_pool, &c->sb_blen, &c->sb_cells, &c->sb_out}) b->release();
     c->hkeys.release();
     c->hbits.release();
     for (hipStream_t st : {c->s_h2d, c->s_comp, c->s_d2h})
@@ -2579,6 +2585,119 @@ extern "C" int seb_registry_multiget_blocks(seb_registry *r, const seb_keys *kb,
     std::vector<uint64_t> by_slot(kRegMaxFiles, UINT64_MAX);
     for (auto &e : r->entries) by_slot[e.slot] = e.file_num;
     for (uint64_t i = 0; i < cand.size(); ++i) files[i] = cand[i] == 0xFFFF ? UINT64_MAX : by_slot[cand[i]];
+    return SEB_OK;
+}
+
+// ------------------------------------------------ batched data-block search (SSTable.Get's last step)
+
+extern "C" int seb_block_search(const uint8_t *block, uint64_t len, const uint8_t *key, uint64_t key_len,
+                                uint32_t *cell) {
+    if (len > SEB_BLOCK_BYTES)
+        return fail(SEB_ERR_INVALID, "seb_block_search: %llu bytes > the 4096 readBlock returns", (unsigned long long)len);
+    if (seb::block_search(block, len, key, key_len, cell) != 0)
+        return fail(SEB_ERR_INVALID, "seb_block_search: null argument");
+    return SEB_OK;
+}
+
+extern "C" int seb_blocks_dedup(const uint64_t *files, const uint64_t *blocks, uint64_t cells, uint32_t *bid,
+                                uint64_t *uniq_files, uint64_t *uniq_blocks, uint64_t uniq_cap, uint64_t *num_uniq) {
+    switch (seb::blocks_dedup(files, blocks, cells, bid, uniq_files, uniq_blocks, uniq_cap, num_uniq)) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_RANGE, "seb_blocks_dedup: %llu distinct blocks > uniq_cap %llu; retry with *num_uniq",
+                    (unsigned long long)*num_uniq, (unsigned long long)uniq_cap);
+    case -3:
+        return fail(SEB_ERR_NOMEM, "seb_blocks_dedup: out of host memory");
+    case -4:
+        return fail(SEB_ERR_INVALID, "seb_blocks_dedup: more than 2^32 - 1 distinct blocks");
+    default:
+        return fail(SEB_ERR_INVALID, "seb_blocks_dedup: null argument");
+    }
+}
+
+static int check_search_args(const seb_keys *keys, const void *bid, uint32_t cap, const uint8_t *pool, const void *blen,
+                             uint32_t num_blocks, const char *who) {
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    if (cap == 0) return fail(SEB_ERR_INVALID, "%s: cap 0", who);
+    if (!bid || (num_blocks && (!pool || !blen))) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_search_blocks(const seb_keys *keys, const uint32_t *bid, uint32_t cap, const uint8_t *pool,
+                                     const uint16_t *blen, uint32_t num_blocks, uint32_t *cells, void *stream) {
+    const char *who = "seb_dev_search_blocks";
+    enter();
+    int rc;
+    if (!pool || !blen || !cells) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if ((rc = check_search_args(keys, bid, cap, pool, blen, num_blocks, who))) return rc;
+    if ((uintptr_t)pool & 15) return fail(SEB_ERR_INVALID, "%s: the block pool is not 16-byte aligned", who);
+    if (keys->n == 0) return SEB_OK;
+    HIP_OR_FAIL(launch_search_blocks(key_batch(keys), bid, cap, pool, blen, num_blocks, cells, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_resolve_rows(const uint32_t *cells, const uint32_t *bid, uint64_t n, uint32_t cap,
+                                    uint8_t *status, uint16_t *col, uint64_t *vloc, uint32_t *vlen, void *stream) {
+    const char *who = "seb_dev_resolve_rows";
+    enter();
+    if (!cells || !bid || !status) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if (cap == 0) return fail(SEB_ERR_INVALID, "%s: cap 0", who);
+    if (n == 0) return SEB_OK;
+    HIP_OR_FAIL(launch_resolve_rows(cells, bid, n, cap, status, col, vloc, vlen, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+// Host buffers through the context: the pool and blen go up once, then a chunk of keys at a time on the
+// compute stream (copy in, search, resolve, copy out), as seb_registry_locate does.
+extern "C" int seb_search_blocks(seb_ctx *c, const seb_keys *kb, const uint32_t *bid, uint32_t cap,
+                                 const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, uint8_t *status,
+                                 uint16_t *col, uint64_t *vloc, uint32_t *vlen, uint32_t *cells) {
+    const char *who = "seb_search_blocks";
+    WsCall ws_call;
+    int rc;
+    if (!c) return fail(SEB_ERR_INVALID, "%s: null ctx", who);
+    if ((rc = check_search_args(kb, bid, cap, pool, blen, num_blocks, who)) || (rc = validate_offsets(kb, who))) return rc;
+    if (!status && kb->n) return fail(SEB_ERR_INVALID, "%s: null status", who);
+    if (kb->n == 0) return SEB_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OR_FAIL(hipSetDevice(c->device));
+    const uint64_t pool_bytes = (uint64_t)num_blocks * SEB_BLOCK_BYTES;
+    if ((rc = c->sb_pool.reserve(std::max<uint64_t>(pool_bytes, 16))) ||
+        (rc = c->sb_blen.reserve(std::max<uint64_t>(2ull * num_blocks, 16))))
+        return rc;
+    if (num_blocks) {
+        HIP_OR_FAIL(hipMemcpyAsync(c->sb_pool.p, pool, pool_bytes, hipMemcpyHostToDevice, c->s_comp));
+        HIP_OR_FAIL(hipMemcpyAsync(c->sb_blen.p, blen, 2ull * num_blocks, hipMemcpyHostToDevice, c->s_comp));
+    }
+    std::vector<Chunk> chunks;
+    plan_chunks(kb, c->chunk_bytes, chunks);
+    for (const Chunk &ch : chunks) {
+        KeyBatch dk{};
+        if ((rc = stage_chunk(c, kb, ch, 0, &dk, true))) return rc;
+        const uint64_t n = dk.n, ncell = n * (uint64_t)cap;
+        // per key: vloc u64, vlen u32, col u16, status u8, each array 16-B aligned
+        const uint64_t o_vlen = (8 * n + 15) & ~15ull, o_col = (o_vlen + 4 * n + 15) & ~15ull,
+                       o_st = (o_col + 2 * n + 15) & ~15ull;
+        if ((rc = c->sb_bid.reserve(ncell * 4)) || (rc = c->sb_cells.reserve(ncell * 4)) ||
+            (rc = c->sb_out.reserve(o_st + n)))
+            return rc;
+        uint8_t *o = (uint8_t *)c->sb_out.p;
+        HIP_OR_FAIL(hipMemcpyAsync(c->sb_bid.p, bid + ch.i0 * cap, ncell * 4, hipMemcpyHostToDevice, c->s_comp));
+        HIP_OR_FAIL(launch_search_blocks(dk, (const uint32_t *)c->sb_bid.p, cap, (const uint8_t *)c->sb_pool.p,
+                                         (const uint16_t *)c->sb_blen.p, num_blocks, (uint32_t *)c->sb_cells.p,
+                                         c->s_comp));
+        HIP_OR_FAIL(launch_resolve_rows((const uint32_t *)c->sb_cells.p, (const uint32_t *)c->sb_bid.p, n, cap, o + o_st,
+                                        (uint16_t *)(o + o_col), (uint64_t *)o, (uint32_t *)(o + o_vlen), c->s_comp));
+        HIP_OR_FAIL(hipMemcpyAsync(status + ch.i0, o + o_st, n, hipMemcpyDeviceToHost, c->s_comp));
+        if (col) HIP_OR_FAIL(hipMemcpyAsync(col + ch.i0, o + o_col, 2 * n, hipMemcpyDeviceToHost, c->s_comp));
+        if (vloc) HIP_OR_FAIL(hipMemcpyAsync(vloc + ch.i0, o, 8 * n, hipMemcpyDeviceToHost, c->s_comp));
+        if (vlen) HIP_OR_FAIL(hipMemcpyAsync(vlen + ch.i0, o + o_vlen, 4 * n, hipMemcpyDeviceToHost, c->s_comp));
+        if (cells)
+            HIP_OR_FAIL(hipMemcpyAsync(cells + ch.i0 * cap, c->sb_cells.p, ncell * 4, hipMemcpyDeviceToHost, c->s_comp));
+        HIP_OR_FAIL(hipStreamSynchronize(c->s_comp));  // the staging buffers are reused by the next chunk
+    }
     return SEB_OK;
 }
 

@@ -149,6 +149,20 @@ constexpr uint64_t kNoBlock = ~0ull;  // SEB_NO_BLOCK
 hipError_t launch_locate(const KeyBatch &kb, const uint16_t *cand, uint32_t cap, const LocSlot *tab, uint32_t ntab,
                          uint64_t *blocks, hipStream_t s);
 
+// seb_search.hip: searchBlock (lsm/sstable.go:242-290) for every cell of a MultiGet's rows, and
+// LSM.Get's decision over each row (lsm/lsm.go:174-197).  Block b of the caller's pool is
+// pool[b * kBlockBytes, b * kBlockBytes + min(blen[b], kBlockBytes)).
+constexpr uint32_t kBlockBytes = 4096;        // SEB_BLOCK_BYTES
+constexpr uint32_t kNoBlockId = 0xFFFFFFFFu;  // SEB_NO_BLOCK_ID
+enum : uint32_t { kCellNone = 0, kCellMiss = 1, kCellFound = 2, kCellTombstone = 3, kCellTrunc = 4 };
+enum : uint8_t { kGetMiss = 0, kGetFound = 1, kGetError = 2 };
+// cells[c] = status << 28 | voff << 13 | vlen for key c / cap in block bid[c]; kCellNone for an id >= nblocks.
+hipError_t launch_search_blocks(const KeyBatch &kb, const uint32_t *bid, uint32_t cap, const uint8_t *pool,
+                                const uint16_t *blen, uint32_t nblocks, uint32_t *cells, hipStream_t s);
+// Per key, the first FOUND or TRUNC cell of its row decides; col / vloc / vlen may be null.
+hipError_t launch_resolve_rows(const uint32_t *cells, const uint32_t *bid, uint64_t n, uint32_t cap, uint8_t *status,
+                               uint16_t *col, uint64_t *vloc, uint32_t *vlen, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

@@ -1,5 +1,5 @@
 // seb_keycmp.h — Go string order on the device, shared by the registry's kernels (seb_multiget.hip:
-// key ranges; seb_locate.hip: sparse-index keys).  A stored key is held as its zero-padded first 16
+// key ranges; seb_locate.hip: sparse-index keys; seb_search.hip: data-block entries).  A stored key is held as its zero-padded first 16
 // bytes in two big-endian words plus its bytes; a batch key's prefix is built once per key.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,6 +27,13 @@ __device__ __forceinline__ void key_prefix(const KeyBatch &kb, const uint8_t *ke
         k0 = be64(key, klen);
         k1 = klen > 8 ? be64(key + 8, klen - 8) : 0ull;
     }
+}
+
+// A little-endian u64 of 8 loaded key bytes as the big-endian word of the key's first min(len, 8)
+// bytes, zero padded (the bytes past len are dropped).
+__device__ __forceinline__ uint64_t be64_of_le(uint64_t le, uint32_t len) {
+    const uint64_t v = __builtin_bswap64(le);
+    return len >= 8 ? v : len == 0 ? 0ull : v & (~0ull << (8 * (8 - len)));
 }
 
 // Go bytewise compare of key (k0,k1 = its first 16 bytes big-endian) vs a stored range key.

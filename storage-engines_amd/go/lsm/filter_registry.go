@@ -6,6 +6,8 @@
 //	LSM.Get's walk + MayContain (lsm/lsm.go:168-198) -> reg.Candidates(keys)
 //	OpenSSTable reads indexData (lsm/sstable.go:105-119)   -> reg.PutIndex(fileNum, indexData)
 //	SSTable.Get's index bisection (lsm/sstable.go:210-222) -> reg.MultiGetBlocks(keys)
+//	readBlock (lsm/sstable.go:225-239) stays with the caller: it reads every BlockRead once
+//	searchBlock + Get's decision (sstable.go:242-290, lsm.go:174-197) -> reg.SearchBlocks(keys, reads, blocks)
 //
 // Not compiled in this repository's pipeline (no Go toolchain in the image); the C ABI it calls is
 // tested through the Python binding (tests/test_gpu_parity.py, test_registry_*).
@@ -20,6 +22,7 @@ import "C"
 
 import (
 	"runtime"
+	"sync"
 	"sync/atomic"
 	"unsafe"
 )
@@ -28,6 +31,9 @@ import (
 type FilterRegistry struct {
 	h       *C.seb_registry
 	capHint atomic.Uint32 // row width of the last Candidates call (the C side re-checks it)
+	device  int
+	ctxMu   sync.Mutex
+	ctx     *C.seb_ctx // SearchBlocks' streams and staging buffers, made on first use
 }
 
 func regPanic(op string) {
@@ -40,8 +46,13 @@ func NewFilterRegistry(device int) *FilterRegistry {
 	if h == nil {
 		regPanic("New")
 	}
-	r := &FilterRegistry{h: h}
-	runtime.SetFinalizer(r, func(r *FilterRegistry) { C.seb_registry_free(r.h) })
+	r := &FilterRegistry{h: h, device: device}
+	runtime.SetFinalizer(r, func(r *FilterRegistry) {
+		if r.ctx != nil {
+			C.seb_ctx_destroy(r.ctx)
+		}
+		C.seb_registry_free(r.h)
+	})
 	return r
 }
 
@@ -189,6 +200,110 @@ func (r *FilterRegistry) MultiGetBlocks(keys []string) [][]BlockRead {
 			if blocks[j] != ^uint64(0) { // SEB_NO_BLOCK: blockIdx == 0, nothing to read
 				out[i] = append(out[i], BlockRead{File: files[j], Offset: blocks[j]})
 			}
+		}
+	}
+	return out
+}
+
+// GetResult is LSM.Get's answer over the SSTables for one key of a SearchBlocks batch.
+type GetResult struct {
+	Found bool   // a file holds a live entry for the key
+	Err   bool   // the deciding block is truncated: searchBlock's "block truncated"
+	Read  int    // index into the key's reads of the block that decided, -1 for none
+	Value []byte // the value (a copy), nil unless Found
+}
+
+// SearchBlocks finishes the batch MultiGetBlocks began.  reads[i] is MultiGetBlocks' answer for keys[i];
+// blocks maps every distinct BlockRead to the bytes readBlock returned for it (at most 4096; the caller
+// does the file reads, each block once).  Per key it walks each block as searchBlock does
+// (lsm/sstable.go:242-290) and decides as LSM.Get does (lsm/lsm.go:174-197): the first file in visiting
+// order that finds the key or fails ends the walk.  A tombstone inside an SSTable does NOT end it
+// (sst.Get returns found == false, sstable.go:273-275), so an older file's value is returned, exactly
+// as the reference does.  One H2D copy, two launches and one D2H copy for the whole batch.
+func (r *FilterRegistry) SearchBlocks(keys []string, reads [][]BlockRead, blocks map[BlockRead][]byte) []GetResult {
+	out := make([]GetResult, len(keys))
+	if len(keys) == 0 {
+		return out
+	}
+	if len(reads) != len(keys) {
+		panic("lsm: FilterRegistry.SearchBlocks: len(reads) != len(keys)")
+	}
+	w := 1
+	for _, row := range reads {
+		if len(row) > w {
+			w = len(row)
+		}
+	}
+	// the block pool: each distinct block once, in first-appearance order, in 4096-byte slots
+	ids := make(map[BlockRead]uint32)
+	var pool []byte
+	var blen []uint16
+	bid := make([]uint32, len(keys)*w)
+	for i := range bid {
+		bid[i] = ^uint32(0) // SEB_NO_BLOCK_ID
+	}
+	for i, row := range reads {
+		for j, rd := range row {
+			id, ok := ids[rd]
+			if !ok {
+				b, have := blocks[rd]
+				if !have || len(b) > 4096 {
+					panic("lsm: FilterRegistry.SearchBlocks: a read's block is missing or longer than 4096 bytes")
+				}
+				id = uint32(len(blen))
+				ids[rd] = id
+				slot := make([]byte, 4096)
+				copy(slot, b)
+				pool = append(pool, slot...)
+				blen = append(blen, uint16(len(b)))
+			}
+			bid[i*w+j] = id
+		}
+	}
+	data, offs := packKeys(keys)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&data[0])
+	pin.Pin(&offs[0])
+	ks := (*C.seb_keys)(C.malloc(C.size_t(unsafe.Sizeof(C.seb_keys{}))))
+	defer C.free(unsafe.Pointer(ks))
+	*ks = C.seb_keys{data: (*C.uint8_t)(unsafe.Pointer(&data[0])), offsets: (*C.uint64_t)(unsafe.Pointer(&offs[0])),
+		n: C.uint64_t(len(keys))}
+	status := make([]uint8, len(keys))
+	col := make([]uint16, len(keys))
+	vloc := make([]uint64, len(keys))
+	vlen := make([]uint32, len(keys))
+	var poolPtr *C.uint8_t
+	var blenPtr *C.uint16_t
+	if len(blen) > 0 {
+		poolPtr = (*C.uint8_t)(unsafe.Pointer(&pool[0]))
+		blenPtr = (*C.uint16_t)(unsafe.Pointer(&blen[0]))
+	}
+	r.ctxMu.Lock()
+	if r.ctx == nil && C.seb_ctx_create(C.int(r.device), &r.ctx) != 0 {
+		r.ctxMu.Unlock()
+		regPanic("SearchBlocks")
+	}
+	rc := C.seb_search_blocks(r.ctx, ks, (*C.uint32_t)(unsafe.Pointer(&bid[0])), C.uint32_t(w), poolPtr, blenPtr,
+		C.uint32_t(len(blen)), (*C.uint8_t)(unsafe.Pointer(&status[0])), (*C.uint16_t)(unsafe.Pointer(&col[0])),
+		(*C.uint64_t)(unsafe.Pointer(&vloc[0])), (*C.uint32_t)(unsafe.Pointer(&vlen[0])), nil)
+	r.ctxMu.Unlock()
+	if rc != 0 {
+		regPanic("SearchBlocks")
+	}
+	runtime.KeepAlive(data)
+	runtime.KeepAlive(offs)
+	for i := range keys {
+		out[i].Read = -1
+		if col[i] != 0xFFFF {
+			out[i].Read = int(col[i])
+		}
+		switch status[i] {
+		case C.SEB_GET_FOUND:
+			out[i].Found = true
+			out[i].Value = append([]byte{}, pool[vloc[i]:vloc[i]+uint64(vlen[i])]...)
+		case C.SEB_GET_ERROR:
+			out[i].Err = true
 		}
 	}
 	return out

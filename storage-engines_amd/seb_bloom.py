@@ -116,6 +116,11 @@ _SIGS = {
     "seb_registry_locate_dev": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp, _vp]),
     "seb_registry_locate": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp]),
     "seb_registry_multiget_blocks": (_i, [_vp, C.POINTER(seb_keys), _vp, _vp, _u32, C.POINTER(_u32)]),
+    "seb_block_search": (_i, [_vp, _u64, _vp, _u64, C.POINTER(_u32)]),
+    "seb_dev_search_blocks": (_i, [C.POINTER(seb_keys), _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "seb_dev_resolve_rows": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "seb_search_blocks": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "seb_blocks_dedup": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "seb_workspace_bytes": (_u64, []),
     "seb_dev_or_slices": (_i, [_vp, _u32, _u64, _vp, _vp]),
     "seb_workspace_release": (_i, []),
@@ -139,6 +144,10 @@ _SIGS = {
 
 WAL_CRC, WAL_SEAL, WAL_VERIFY = 0, 1, 2
 NO_BLOCK = 2**64 - 1  # SEB_NO_BLOCK: no index entry <= the key, a padded cell, or a slot without a file
+BLOCK_BYTES = 4096    # SEB_BLOCK_BYTES: a block pool slot (readBlock returns at most this many bytes)
+NO_BLOCK_ID = 2**32 - 1  # SEB_NO_BLOCK_ID: a cell without a block to search
+CELL_NONE, CELL_MISS, CELL_FOUND, CELL_TOMBSTONE, CELL_TRUNC = range(5)
+GET_MISS, GET_FOUND, GET_ERROR = range(3)
 
 
 def build_library() -> str:
@@ -295,6 +304,31 @@ class Ctx:
         bits = np.ascontiguousarray(bits, dtype=np.uint8)
         check(lib().seb_probe(self._p, kb.ref, bits.ctypes.data, m, k, out.ctypes.data))
         return out[: kb.n]
+
+    def search_blocks(self, keys, bid: np.ndarray, pool: np.ndarray, blen: np.ndarray, want_cells: bool = False):
+        """Host form of the block search: bid is the (n, cap) u32 block ids, pool the blocks in
+        4096-byte slots (host bytes), blen their lengths.  Returns (status u8, col u16, vloc u64,
+        vlen u32) per key, plus the (n, cap) u32 cell results with want_cells."""
+        kb = as_keys(keys)
+        bid = np.ascontiguousarray(bid, dtype=np.uint32)
+        if bid.ndim != 2 or bid.shape[0] != kb.n:
+            raise ValueError("bid must be an (n, cap) array of u32 block ids")
+        cap = bid.shape[1]
+        pool = np.ascontiguousarray(pool, dtype=np.uint8).reshape(-1)
+        blen = np.ascontiguousarray(blen, dtype=np.uint16)
+        nb = blen.size
+        if pool.size < nb * BLOCK_BYTES:
+            raise ValueError(f"pool holds {pool.size} bytes, {nb} blocks need {nb * BLOCK_BYTES}")
+        n1 = max(kb.n, 1)
+        status, col = np.zeros(n1, np.uint8), np.zeros(n1, np.uint16)
+        vloc, vlen = np.zeros(n1, np.uint64), np.zeros(n1, np.uint32)
+        cells = np.zeros((n1, max(cap, 1)), np.uint32)
+        src = bid if bid.size else np.zeros(1, np.uint32)
+        check(lib().seb_search_blocks(self._p, kb.ref, src.ctypes.data, cap, pool.ctypes.data if nb else None,
+                                      blen.ctypes.data if nb else None, nb, status.ctypes.data, col.ctypes.data,
+                                      vloc.ctypes.data, vlen.ctypes.data, cells.ctypes.data if want_cells else None))
+        out = (status[: kb.n], col[: kb.n], vloc[: kb.n], vlen[: kb.n])
+        return out + (cells[: kb.n, :cap],) if want_cells else out
 
     def probe_multi(self, keys, filters: list[tuple[np.ndarray, int, int]]) -> np.ndarray:
         kb = as_keys(keys)
@@ -694,6 +728,88 @@ def dev_wal_crc(data, rec_off, mode: int = WAL_CRC, crc=None, ok=None, stream=No
     VERIFY sets ok[i] (framing + stored CRC, lsm/wal.go:123-133)."""
     check(lib().seb_dev_wal_crc(data.data_ptr(), rec_off.data_ptr(), rec_off.numel() - 1, mode, _ptr(crc), _ptr(ok),
                                 _stream(stream)))
+
+
+# ------------------------------- batched data-block search (SSTable.Get's last step, lsm/sstable.go:242-290)
+
+def cell_unpack(cell) -> tuple:
+    """(status, voff, vlen) of a u32 cell result (status << 28 | voff << 13 | vlen); arrays give arrays."""
+    c = np.asarray(cell, dtype=np.uint32) if isinstance(cell, np.ndarray) else int(cell)
+    return c >> 28, (c >> 13) & 0x1FFF, c & 0x1FFF
+
+
+def block_search(block: bytes, key: bytes) -> int:
+    """searchBlock's walk on the host for one block image (at most 4096 bytes) and one key: the u32
+    cell result.  "block truncated" is the status CELL_TRUNC, not an error."""
+    cell = _u32(0)
+    check(lib().seb_block_search(bytes(block), len(block), bytes(key), len(key), C.byref(cell)))
+    return cell.value
+
+
+def blocks_dedup(files: np.ndarray, blocks: np.ndarray) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """multiget_blocks' parallel (file, block offset) arrays into the read list: (bid, uniq_files,
+    uniq_blocks) with each distinct pair once in first-appearance order and bid (u32, the shape of
+    `files`) its position per cell, NO_BLOCK_ID where the block is NO_BLOCK."""
+    files = np.ascontiguousarray(files, dtype=np.uint64)
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+    if files.shape != blocks.shape:
+        raise ValueError("files and blocks must have one shape")
+    cells = files.size
+    bid = np.zeros(max(cells, 1), np.uint32)
+    need = _u64(0)
+    cap = max(min(cells, 1024), 1)
+    while True:
+        uf, ub = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        rc = lib().seb_blocks_dedup(files.ctypes.data if cells else None, blocks.ctypes.data if cells else None, cells,
+                                    bid.ctypes.data, uf.ctypes.data, ub.ctypes.data, cap, C.byref(need))
+        if rc == -4 and need.value > cap:
+            cap = need.value
+            continue
+        check(rc)
+        return bid[:cells].reshape(files.shape), uf[: need.value], ub[: need.value]
+
+
+def _nbytes(t) -> int:
+    return t.numel() * t.element_size()
+
+
+def dev_search_blocks(keys: seb_keys, bid, cap: int, pool, blen, cells, num_blocks: int | None = None,
+                      stream=None) -> None:
+    """Device form: cells[c] (n * cap u32) = the block search of pool block bid[c] (u32) for key
+    c // cap; pool holds num_blocks (default: blen.numel()) slots of 4096 bytes, blen (u16) their
+    lengths.  Not synchronised."""
+    ncell = keys.n * cap
+    nb = blen.numel() if num_blocks is None else num_blocks
+    if blen.element_size() != 2 or blen.numel() < nb:
+        raise ValueError(f"blen holds {blen.numel()} lengths of {blen.element_size()} bytes, {nb} blocks need {nb} u16")
+    if _nbytes(bid) < 4 * ncell:
+        raise ValueError(f"bid holds {_nbytes(bid)} bytes, n * cap u32 cells need {4 * ncell}")
+    if _nbytes(cells) < 4 * ncell:
+        raise ValueError(f"cells holds {_nbytes(cells)} bytes, n * cap u32 cells need {4 * ncell}")
+    if _nbytes(pool) < BLOCK_BYTES * nb:
+        raise ValueError(f"pool holds {_nbytes(pool)} bytes, {nb} blocks need {BLOCK_BYTES * nb}")
+    check(lib().seb_dev_search_blocks(C.byref(keys), bid.data_ptr(), cap, pool.data_ptr(), blen.data_ptr(), nb,
+                                      cells.data_ptr(), _stream(stream)))
+
+
+def dev_resolve_rows(cells, bid, n: int, cap: int, status, col=None, vloc=None, vlen=None, stream=None) -> None:
+    """Device form of LSM.Get's decision per row of cells: status (n u8), and optionally col (n u16),
+    vloc (n u64: the value's byte offset in the pool) and vlen (n u32).  Not synchronised."""
+    for name, t, size in (("cells", cells, 4 * n * cap), ("bid", bid, 4 * n * cap), ("status", status, n),
+                          ("col", col, 2 * n), ("vloc", vloc, 8 * n), ("vlen", vlen, 4 * n)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {n} keys x {cap} cells need {size}")
+    check(lib().seb_dev_resolve_rows(cells.data_ptr(), bid.data_ptr(), n, cap, status.data_ptr(), _ptr(col), _ptr(vloc),
+                                     _ptr(vlen), _stream(stream)))
+
+
+def search_blocks(keys, bid: np.ndarray, pool: np.ndarray, blen: np.ndarray, want_cells: bool = False, device: int = 0):
+    """Ctx.search_blocks on a context made for the call."""
+    ctx = Ctx(device)
+    try:
+        return ctx.search_blocks(keys, bid, pool, blen, want_cells)
+    finally:
+        ctx.close()
 
 
 def index_scan(block: bytes) -> int:

@@ -25,6 +25,7 @@ for f in $(cd $C && ls *.hip | sed "s/\.hip$//"); do
 done
 /opt/rocm/bin/hipcc $FL -c $C/seb_host.cpp -o $OUT/obj/seb_host.o &
 g++ -O2 -std=c++17 -fPIC -ffp-contract=off -c $C/seb_sizing.cpp -o $OUT/obj/seb_sizing.o &
+g++ -O2 -std=c++17 -fPIC -c $C/seb_block.cpp -o $OUT/obj/seb_block.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libseb_bloom.so $OUT/obj/*.o -Wl,-rpath,/opt/rocm/lib
 echo "$OUT/libseb_bloom.so"
