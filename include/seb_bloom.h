@@ -421,6 +421,80 @@ int seb_search_blocks(seb_ctx *ctx, const seb_keys *keys, const uint32_t *bid, u
 int seb_blocks_dedup(const uint64_t *files, const uint64_t *blocks, uint64_t cells, uint32_t *bid,
                      uint64_t *uniq_files, uint64_t *uniq_blocks, uint64_t uniq_cap, uint64_t *num_uniq);
 
+/* ------------- batched SSTable builder: data blocks, index block, metadata and the file image ---- */
+/* What SSTableBuilder computes between its Write calls (lsm/sstable_builder.go:42-135,185-290), for a sorted
+ * run that is already in memory: entry i has key i of `keys`, value vals[val_off[i], val_off[i+1]) (n + 1
+ * non-decreasing offsets, val_off[0] may be != 0) and the flag deleted[i] (any non-zero byte is "deleted";
+ * deleted == NULL: none).  The library writes no file; the order of the entries is never checked.
+ *
+ * Entry image: [keySize u32][valueSize u32][deleted u8 = 1 or 0][key][value], little-endian,
+ * e = 9 + keySize + valueSize bytes.  A block is [numEntries u32] then its entries.  The cut is greedy: before
+ * an entry is appended, a block of more than 4 bytes that the entry would take past 4096 is flushed.  With P
+ * the 64-bit prefix sum of e, the block that starts at entry s ends before the smallest t > s with
+ * 4 + (P[t+1] - P[s]) > 4096; entry s always belongs to it.  A flushed block shorter than 4096 bytes is zero
+ * padded to 4096; its index entry is (its first key, the offset it was written at).  An entry with
+ * 4 + e > 4096 ("oversized") is a block of its own, longer than 4096 bytes and written unpadded, and every
+ * later block offset of the file stops being a multiple of 4096 (the reference cannot read such a block back,
+ * but the bytes it writes are defined, and the host half writes them).
+ *
+ * Finish: the index block [numEntries u32] then per block [keySize u32][blockOffset u64][key]; the metadata
+ * [minKeySize u32][maxKeySize u32][minKey][maxKey] with min / max = the first and the last key added (8 zero
+ * bytes for an empty file); the filter's Encode(); the 28-byte footer [indexOffset u64][bloomOffset u64]
+ * [metadataOffset u64][0x5354424C u32].  A file without entries is a 4-byte index, 8 bytes of metadata, the
+ * empty filter and the footer.
+ *
+ * With no oversized entry the data section is the block pool of the block search above: block b at
+ * b * 4096, its true length in a u16 array, so a block is searchable the moment it is written. */
+typedef struct seb_sst_sizes {
+    uint64_t num_blocks;       /* data blocks = index entries */
+    uint64_t data_bytes;       /* the data section: 4096 per block, more for an oversized one */
+    uint64_t index_bytes;      /* 4 + per block 12 + its first key's length */
+    uint64_t meta_bytes;       /* 8 + the first and the last key's lengths */
+    uint64_t oversize_entries; /* entries with 4 + e > 4096 */
+} seb_sst_sizes;
+#define SEB_SST_FOOTER_BYTES 28u
+#define SEB_SST_MAGIC 0x5354424Cu
+
+/* Host only: one file.  seb_sst_plan sizes the three sections; seb_sst_encode writes them (a capacity below
+ * the section's size: SEB_ERR_RANGE, nothing meaningful written; *sizes, nullable, is filled either way) and
+ * is the reference for the device form, the path for files the device refuses and what a caller without a GPU
+ * uses.  A key or a value of 2^32 bytes or more, or decreasing offsets: SEB_ERR_INVALID. */
+int seb_sst_plan(const seb_keys *keys, const uint64_t *val_off, seb_sst_sizes *sizes);
+int seb_sst_encode(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                   uint8_t *data, uint64_t data_cap, uint8_t *index, uint64_t index_cap, uint8_t *meta,
+                   uint64_t meta_cap, seb_sst_sizes *sizes);
+int seb_sst_footer(uint64_t index_offset, uint64_t bloom_offset, uint64_t metadata_offset, uint8_t *out28);
+
+/* Device pointers, many files in one call (a compaction's output files, lsm/compaction.go:253): file f holds
+ * entries [file_begin[f], file_begin[f+1]) of the batch; file_begin is a HOST array of num_files + 1
+ * non-decreasing entries from 0 to keys->n.  Keys in every seb_keys layout, any byte alignment; n < 2^32.
+ * The workspace (seb_dev_sst_workspace_size bytes of device memory, 16-byte aligned, opaque) carries the plan
+ * from the first call to the second and must not be touched in between.
+ * seb_dev_sst_plan runs the cut for every file, SYNCHRONISES the stream and fills the host array
+ * sizes[num_files], so the caller can allocate the outputs.
+ * seb_dev_sst_encode (not synchronised; `sizes` as the plan returned them) writes every file's data section
+ * back to back (file f at the sum of the earlier data_bytes, so block b of the call at b * 4096), blen
+ * (nullable): each block's true length as the pool's u16, the index blocks back to back and the metadata back
+ * to back.  Outputs need not be cleared (the zero padding is written) and nothing is written outside the
+ * stated sizes; `data` must be 16-byte aligned.  The device never writes a block longer than 4096 bytes: a
+ * file with oversize_entries > 0 makes encode return SEB_ERR_RANGE naming the file (use the host half).
+ * Files of 0 entries (0 blocks, a 4-byte index) and of 1 entry are valid; n == 0 launches nothing. */
+uint64_t seb_dev_sst_workspace_size(uint64_t n, uint32_t num_files);
+int seb_dev_sst_plan(const seb_keys *keys, const uint64_t *val_off, const uint64_t *file_begin, uint32_t num_files,
+                     void *workspace, uint64_t workspace_bytes, seb_sst_sizes *sizes, void *stream);
+int seb_dev_sst_encode(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                       const uint64_t *file_begin, uint32_t num_files, const seb_sst_sizes *sizes,
+                       const void *workspace, uint64_t workspace_bytes, uint8_t *data, uint16_t *blen,
+                       uint8_t *index, uint8_t *meta, void *stream);
+/* The host-buffer form on a context: one file, host memory, synchronous.  `out` receives the complete file
+ * image, byte-identical to what SSTableBuilder leaves on disk: data, index, metadata, the Encode() of
+ * NewBloomFilter(expected_keys, 0.01) with every key added, the footer.  *need (nullable) = its size; cap
+ * below it: SEB_ERR_RANGE (retry with *need, as seb_registry_multiget_blocks).  A file with an oversized entry
+ * goes through the host half, the filter still through the device.  expected_keys == 0 with n > 0:
+ * SEB_ERR_INVALID (the reference's Add would take a remainder by zero). */
+int seb_sst_build(seb_ctx *ctx, const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off,
+                  const uint8_t *deleted, int64_t expected_keys, uint8_t *out, uint64_t cap, uint64_t *need);
+
 /* ---------- hash-index shard routing + WAL record checksums (off the bloom path) ---- */
 /* shard[i] = FNV-1a32(key i) & ((1 << shard_bits) - 1), the reference's getShard
  * (hashindex/shard.go:47-52; 256 shards = shard_bits 8).  hash[i] (nullable) = the full FNV-1a32.

@@ -1,7 +1,8 @@
 // seb_block.cpp — the host side of the batched data-block search: searchBlock's walk
-// (lsm/sstable.go:242-290) for one block image and one key, and the read-list builder.  No HIP
-// dependency, so it compiles alone (tools/sanitize/block_check.cpp); the C ABI wrappers that set
-// seb_last_error are in seb_host.cpp.
+// (lsm/sstable.go:242-290) for one block image and one key, and the read-list builder; and the host
+// half of the batched SSTable builder (below).  No HIP dependency, so it compiles alone
+// (tools/sanitize/block_check.cpp, sst_check.cpp); the C ABI wrappers that set seb_last_error are in
+// seb_host.cpp.
 //
 //   numEntries := u32(block[0:4]); off := 4                              sstable.go:243-248
 //   for i := 0; i < numEntries; i++ {
@@ -17,6 +18,8 @@
 #include <cstring>
 #include <new>
 #include <unordered_map>
+
+#include "seb_block.h"
 
 namespace seb {
 
@@ -102,6 +105,104 @@ int blocks_dedup(const uint64_t *files, const uint64_t *blocks, uint64_t cells, 
     } catch (const std::bad_alloc &) {
         return -3;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The host half of the batched SSTable builder: SSTableBuilder.Add / flushBlock / Finish /
+// encodeIndex / encodeMetadata (lsm/sstable_builder.go:42-135,185-290) for one sorted run in memory.
+//
+//   Add:   entry = [keySize u32][valueSize u32][deleted u8][key][value]              :55-74
+//          if len(cur)+len(entry) > 4096 { flushBlock() }   (a no-op while len(cur) <= 4)  :77-82,92
+//          cur = append(cur, entry...)
+//   flush: cur[0:4] = numEntries; write cur; index += (first key, blockOffset);       :104-120
+//          blockOffset += len(cur); a block shorter than 4096 is zero padded to it     :123-130
+// One walk serves both entry points: out == nullptr only sizes.
+
+static inline void put32(uint8_t *p, uint32_t v) {
+    p[0] = (uint8_t)v, p[1] = (uint8_t)(v >> 8), p[2] = (uint8_t)(v >> 16), p[3] = (uint8_t)(v >> 24);
+}
+static inline void put64(uint8_t *p, uint64_t v) {
+    put32(p, (uint32_t)v);
+    put32(p + 4, (uint32_t)(v >> 32));
+}
+
+// 0; -1 a null argument; -2 a key or value of 2^32 bytes or more, or decreasing offsets; -3 a capacity
+// below its section (sizes are still filled).
+int sst_walk(const SstKeys &k, const uint8_t *vals, const uint64_t *voff, const uint8_t *deleted, const SstOut *out,
+             SstSizes *sz) {
+    if (!sz || (k.n && !voff)) return -1;
+    SstSizes s{0, 0, 4, 8, 0};
+    const uint64_t n = k.n;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (k.off(i + 1) < k.off(i) || voff[i + 1] < voff[i]) return -2;
+        if (k.off(i + 1) - k.off(i) > UINT32_MAX || voff[i + 1] - voff[i] > UINT32_MAX) return -2;
+    }
+    if (n && !k.data && k.off(n) != k.off(0)) return -1;
+    // pass 1: the cut alone (sizes), pass 2: the bytes; the same loop with and without stores
+    for (int pass = 0; pass < (out ? 2 : 1); ++pass) {
+        const bool wr = pass == 1;
+        if (wr && (s.data_bytes > out->data_cap || s.index_bytes > out->index_cap || s.meta_bytes > out->meta_cap)) {
+            *sz = s;
+            return -3;
+        }
+        if (wr && ((s.data_bytes && (!out->data || (!vals && voff[n] != voff[0]))) || !out->index || !out->meta)) return -1;
+        uint64_t at = 0, iat = 4, blocks = 0, oversize = 0;  // data offset, index offset
+        uint64_t i = 0;
+        while (i < n) {
+            // the block that starts at entry i: entries [i, j)
+            uint64_t len = 4, j = i;
+            while (j < n) {
+                const uint64_t e = 9 + (k.off(j + 1) - k.off(j)) + (voff[j + 1] - voff[j]);
+                if (len + e > kBlockBytes && len > 4) break;
+                len += e;
+                ++j;
+                if (e + 4 > kBlockBytes) ++oversize;
+            }
+            const uint64_t klen0 = k.off(i + 1) - k.off(i);
+            if (wr) {
+                uint8_t *b = out->data + at;
+                put32(b, (uint32_t)(j - i));
+                uint64_t o = 4;
+                for (uint64_t t = i; t < j; ++t) {
+                    const uint64_t ks = k.off(t + 1) - k.off(t), vs = voff[t + 1] - voff[t];
+                    put32(b + o, (uint32_t)ks);
+                    put32(b + o + 4, (uint32_t)vs);
+                    b[o + 8] = deleted && deleted[t] ? 1 : 0;
+                    if (ks) memcpy(b + o + 9, k.data + k.off(t), ks);
+                    if (vs) memcpy(b + o + 9 + ks, vals + voff[t], vs);
+                    o += 9 + ks + vs;
+                }
+                if (len < kBlockBytes) memset(b + len, 0, kBlockBytes - len);
+                uint8_t *x = out->index + iat;
+                put32(x, (uint32_t)klen0);
+                put64(x + 4, at);
+                if (klen0) memcpy(x + 12, k.data + k.off(i), klen0);
+            }
+            at += len < kBlockBytes ? kBlockBytes : len;
+            iat += 12 + klen0;
+            ++blocks;
+            i = j;
+        }
+        const uint64_t kmin = n ? k.off(1) - k.off(0) : 0, kmax = n ? k.off(n) - k.off(n - 1) : 0;
+        if (wr) {
+            put32(out->index, (uint32_t)blocks);
+            put32(out->meta, (uint32_t)kmin);
+            put32(out->meta + 4, (uint32_t)kmax);
+            if (kmin) memcpy(out->meta + 8, k.data + k.off(0), kmin);
+            if (kmax) memcpy(out->meta + 8 + kmin, k.data + k.off(n - 1), kmax);
+        }
+        s = SstSizes{blocks, at, iat, 8 + kmin + kmax, oversize};
+    }
+    *sz = s;
+    return 0;
+}
+
+// [indexOffset u64][bloomOffset u64][metadataOffset u64][magic u32]      sstable_builder.go:223-228
+void sst_footer(uint64_t index_offset, uint64_t bloom_offset, uint64_t metadata_offset, uint8_t *out28) {
+    put64(out28, index_offset);
+    put64(out28 + 8, bloom_offset);
+    put64(out28 + 16, metadata_offset);
+    put32(out28 + 24, 0x5354424Cu);
 }
 
 }  // namespace seb

@@ -163,6 +163,27 @@ hipError_t launch_search_blocks(const KeyBatch &kb, const uint32_t *bid, uint32_
 hipError_t launch_resolve_rows(const uint32_t *cells, const uint32_t *bid, uint64_t n, uint32_t cap, uint8_t *status,
                                uint16_t *col, uint64_t *vloc, uint32_t *vlen, hipStream_t s);
 
+// seb_sst.hip: the batched SSTable builder (lsm/sstable_builder.go:42-135,185-290): the block cut of many
+// files (entries [file_begin[f], file_begin[f+1]) of one batch), then their data blocks, index blocks and
+// metadata.  The plan lives in a caller-provided workspace: offsets of its arrays, all 16-byte aligned.
+constexpr uint32_t kSstTile = 1024;  // entries per tile of the cut; > 454, the most a block holds
+struct SstWs {
+    uint64_t bytes, tiles;
+    uint64_t fbeg, ovs_cnt, ovs_exc, fbk, fix, sizes, meta_len;      // per file
+    uint64_t entry, tile_cnt, tile_base, tile_ix, tile_ixbase;       // per tile
+    uint64_t nxt, ex, tix, blk_first;                                // per entry / per block
+};
+SstWs sst_ws_layout(uint64_t n, uint32_t num_files);
+// n >= 1, num_files >= 1, n < 2^32.  Synchronises the stream; sizes_host: num_files x seb_sst_sizes.
+hipError_t launch_sst_plan(const KeyBatch &kb, const uint64_t *voff, const uint64_t *file_begin_host, uint32_t num_files,
+                           void *ws, void *sizes_host, hipStream_t s);
+// A plan without oversized entries; nblocks / index_total / meta_total: the sums of the plan's sizes, past
+// which nothing is written.
+hipError_t launch_sst_encode(const KeyBatch &kb, const uint8_t *vals, const uint64_t *voff, const uint8_t *deleted,
+                             uint32_t num_files, const void *ws, uint64_t nblocks, uint64_t index_total,
+                             uint64_t meta_total, uint8_t *data, uint16_t *blen, uint8_t *index, uint8_t *meta,
+                             hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

@@ -44,6 +44,14 @@ class seb_keys(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class seb_sst_sizes(C.Structure):
+    _fields_ = [("num_blocks", C.c_uint64), ("data_bytes", C.c_uint64), ("index_bytes", C.c_uint64),
+                ("meta_bytes", C.c_uint64), ("oversize_entries", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.num_blocks, self.data_bytes, self.index_bytes, self.meta_bytes, self.oversize_entries)
+
+
 class seb_filter_ref(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("num_bits", C.c_uint64), ("num_hashes", C.c_uint32),
                 ("reserved", C.c_uint32)]
@@ -121,6 +129,14 @@ _SIGS = {
     "seb_dev_resolve_rows": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "seb_search_blocks": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "seb_blocks_dedup": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "seb_sst_plan": (_i, [C.POINTER(seb_keys), _vp, C.POINTER(seb_sst_sizes)]),
+    "seb_sst_encode": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(seb_sst_sizes)]),
+    "seb_sst_footer": (_i, [_u64, _u64, _u64, _vp]),
+    "seb_dev_sst_workspace_size": (_u64, [_u64, _u32]),
+    "seb_dev_sst_plan": (_i, [C.POINTER(seb_keys), _vp, C.POINTER(_u64), _u32, _vp, _u64, C.POINTER(seb_sst_sizes), _vp]),
+    "seb_dev_sst_encode": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, C.POINTER(_u64), _u32, C.POINTER(seb_sst_sizes), _vp,
+                                _u64, _vp, _vp, _vp, _vp, _vp]),
+    "seb_sst_build": (_i, [_vp, C.POINTER(seb_keys), _vp, _vp, _vp, C.c_int64, _vp, _u64, C.POINTER(_u64)]),
     "seb_workspace_bytes": (_u64, []),
     "seb_dev_or_slices": (_i, [_vp, _u32, _u64, _vp, _vp]),
     "seb_workspace_release": (_i, []),
@@ -329,6 +345,25 @@ class Ctx:
                                       vloc.ctypes.data, vlen.ctypes.data, cells.ctypes.data if want_cells else None))
         out = (status[: kb.n], col[: kb.n], vloc[: kb.n], vlen[: kb.n])
         return out + (cells[: kb.n, :cap],) if want_cells else out
+
+    def sst_build(self, keys, vals, val_off, deleted=None, expected_keys: int | None = None) -> bytes:
+        """The complete SSTable file image SSTableBuilder leaves on disk for the run (keys, values
+        vals[val_off[i]:val_off[i+1]], deleted bytes): data blocks, index, metadata, the Encode() of
+        NewBloomFilter(expected_keys, 0.01) with every key added (default: the entry count), footer."""
+        kb = _sst_keys(keys)
+        vals, val_off, deleted = _sst_host_args(kb, vals, val_off, deleted)
+        expected = kb.n if expected_keys is None else expected_keys
+        need = _u64(0)
+        out = np.zeros(1, np.uint8)
+        while True:
+            rc = lib().seb_sst_build(self._p, kb.ref, vals.ctypes.data, val_off.ctypes.data,
+                                     deleted.ctypes.data if deleted is not None else None, expected, out.ctypes.data,
+                                     out.size, C.byref(need))
+            if rc == -4 and need.value > out.size:
+                out = np.zeros(need.value, np.uint8)
+                continue
+            check(rc)
+            return out[: need.value].tobytes()
 
     def probe_multi(self, keys, filters: list[tuple[np.ndarray, int, int]]) -> np.ndarray:
         kb = as_keys(keys)
@@ -808,6 +843,119 @@ def search_blocks(keys, bid: np.ndarray, pool: np.ndarray, blen: np.ndarray, wan
     ctx = Ctx(device)
     try:
         return ctx.search_blocks(keys, bid, pool, blen, want_cells)
+    finally:
+        ctx.close()
+
+
+# ------------------------------- batched SSTable builder (lsm/sstable_builder.go:42-135,185-290)
+
+SST_FOOTER_BYTES = 28
+SST_MAGIC = 0x5354424C
+SST_TILE = 1024  # kSstTile: entries per tile of the device cut (tests place runs around it)
+
+
+def _sst_keys(keys) -> HostKeys:
+    kb = as_keys(keys)
+    if kb.offsets is not None and kb.data.size == 0:  # a run of empty keys still needs a data pointer
+        kb = HostKeys(np.zeros(1, np.uint8), kb.offsets)
+    return kb
+
+
+def _sst_host_args(kb: HostKeys, vals, val_off, deleted):
+    vals = np.ascontiguousarray(vals, dtype=np.uint8).reshape(-1)
+    if vals.size == 0:
+        vals = np.zeros(1, np.uint8)
+    val_off = np.ascontiguousarray(val_off, dtype=np.uint64)
+    if val_off.shape != (kb.n + 1,):
+        raise ValueError(f"val_off must hold n + 1 = {kb.n + 1} offsets")
+    if deleted is not None:
+        deleted = np.ascontiguousarray(deleted, dtype=np.uint8)
+        if deleted.shape != (kb.n,):
+            raise ValueError(f"deleted must hold n = {kb.n} bytes")
+        if kb.n == 0:
+            deleted = None
+    return vals, val_off, deleted
+
+
+def sst_plan(keys, val_off) -> tuple[int, int, int, int, int]:
+    """The builder's cut on the host: (num_blocks, data_bytes, index_bytes, meta_bytes,
+    oversize_entries) of one file."""
+    kb = _sst_keys(keys)
+    val_off = np.ascontiguousarray(val_off, dtype=np.uint64)
+    if val_off.shape != (kb.n + 1,):
+        raise ValueError(f"val_off must hold n + 1 = {kb.n + 1} offsets")
+    sz = seb_sst_sizes()
+    check(lib().seb_sst_plan(kb.ref, val_off.ctypes.data, C.byref(sz)))
+    return sz.as_tuple()
+
+
+def sst_encode(keys, vals, val_off, deleted=None) -> tuple[bytes, bytes, bytes]:
+    """The host half: (data section, index block, metadata) of one file, oversized blocks included."""
+    kb = _sst_keys(keys)
+    vals, val_off, deleted = _sst_host_args(kb, vals, val_off, deleted)
+    _, d, x, m, _ = sst_plan(kb, val_off)
+    data, index, meta = np.zeros(max(d, 1), np.uint8), np.zeros(x, np.uint8), np.zeros(m, np.uint8)
+    check(lib().seb_sst_encode(kb.ref, vals.ctypes.data, val_off.ctypes.data,
+                               deleted.ctypes.data if deleted is not None else None, data.ctypes.data, d,
+                               index.ctypes.data, x, meta.ctypes.data, m, None))
+    return data[:d].tobytes(), index.tobytes(), meta.tobytes()
+
+
+def sst_footer(index_offset: int, bloom_offset: int, metadata_offset: int) -> bytes:
+    out = np.zeros(SST_FOOTER_BYTES, np.uint8)
+    check(lib().seb_sst_footer(index_offset, bloom_offset, metadata_offset, out.ctypes.data))
+    return out.tobytes()
+
+
+def dev_sst_workspace_size(n: int, num_files: int) -> int:
+    return lib().seb_dev_sst_workspace_size(n, num_files)
+
+
+def dev_sst_plan(keys: seb_keys, val_off, file_begin: list[int], ws, stream=None) -> list[tuple[int, int, int, int, int]]:
+    """Device form: the cut of every file (entries [file_begin[f], file_begin[f+1]) of the batch) into
+    the workspace tensor `ws`; synchronises and returns each file's (num_blocks, data_bytes,
+    index_bytes, meta_bytes, oversize_entries)."""
+    nf = len(file_begin) - 1
+    if _nbytes(val_off) < 8 * (keys.n + 1):
+        raise ValueError(f"val_off holds {_nbytes(val_off)} bytes, n + 1 u64 offsets need {8 * (keys.n + 1)}")
+    want = dev_sst_workspace_size(keys.n, max(nf, 0))
+    if _nbytes(ws) < want:
+        raise ValueError(f"workspace holds {_nbytes(ws)} bytes, dev_sst_workspace_size gives {want}")
+    fb = (_u64 * (nf + 1))(*file_begin)
+    sizes = (seb_sst_sizes * max(nf, 1))()
+    check(lib().seb_dev_sst_plan(C.byref(keys), val_off.data_ptr(), fb, nf, ws.data_ptr(), _nbytes(ws), sizes,
+                                 _stream(stream)))
+    return [sizes[f].as_tuple() for f in range(nf)]
+
+
+def dev_sst_encode(keys: seb_keys, vals, val_off, deleted, file_begin: list[int], sizes, ws, data, index, meta,
+                   blen=None, stream=None) -> None:
+    """Device form: writes the files' data sections back to back into `data` (block b at b * 4096),
+    their true lengths into blen (u16, optional), the index blocks into `index` and the metadata into
+    `meta`; `sizes` as dev_sst_plan returned them.  Not synchronised."""
+    nf = len(file_begin) - 1
+    if len(sizes) != nf:
+        raise ValueError("one sizes tuple per file")
+    blocks = sum(s[0] for s in sizes)
+    for name, t, size in (("data", data, sum(s[1] for s in sizes)), ("index", index, sum(s[2] for s in sizes)),
+                          ("meta", meta, sum(s[3] for s in sizes)), ("blen", blen, 2 * blocks),
+                          ("val_off", val_off, 8 * (keys.n + 1)), ("deleted", deleted, keys.n)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, the plan needs {size}")
+    if blen is not None and blen.element_size() != 2:
+        raise ValueError("blen must be a 16-bit tensor")
+    fb = (_u64 * (nf + 1))(*file_begin)
+    cs = (seb_sst_sizes * max(nf, 1))(*[seb_sst_sizes(*s) for s in sizes])
+    check(lib().seb_dev_sst_encode(C.byref(keys), _ptr(vals), val_off.data_ptr(), _ptr(deleted), fb, nf, cs,
+                                   ws.data_ptr(), _nbytes(ws), data.data_ptr(), _ptr(blen), index.data_ptr(),
+                                   meta.data_ptr(), _stream(stream)))
+
+
+def sst_build(keys, vals, val_off, deleted=None, expected_keys: int | None = None, device: int = 0) -> bytes:
+    """Ctx.sst_build on a context made for the call."""
+    ctx = Ctx(device)
+    try:
+        return ctx.sst_build(keys, vals, val_off, deleted, expected_keys)
     finally:
         ctx.close()
 
