@@ -2,7 +2,7 @@
 // (lsm/sstable.go:242-290) for one block image and one key, and the read-list builder; and the host
 // half of the batched SSTable builder (below).  No HIP dependency, so it compiles alone
 // (tools/sanitize/block_check.cpp, sst_check.cpp); the C ABI wrappers that set seb_last_error are in
-// seb_host.cpp.
+// seb_sstable.cpp.
 //
 //   numEntries := u32(block[0:4]); off := 4                              sstable.go:243-248
 //   for i := 0; i < numEntries; i++ {

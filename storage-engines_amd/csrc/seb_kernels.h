@@ -5,7 +5,7 @@
 
 namespace seb {
 
-// Reduction constants for one filter, computed on the host (seb_host.cpp: mod_arg()).
+// Reduction constants for one filter, computed on the host (seb_host.h: mod_arg()).
 struct ModArg {
     uint64_t m;   // numBits (>= 1)
     uint64_t mu;  // floor((2^64 - 1) / m)

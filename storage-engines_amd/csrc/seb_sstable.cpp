@@ -1,0 +1,321 @@
+// seb_sstable.cpp — the entry points of the batched data-block search and of the batched SSTable
+// builder: the C ABI over their host halves (seb_block.cpp) and their kernels (seb_search.hip,
+// seb_sst.hip), and the host-buffer forms through a context.
+#include "seb_block.h"
+#include "seb_host.h"
+
+using namespace seb;
+
+// ------------------------------------------------ batched data-block search (SSTable.Get's last step)
+
+extern "C" int seb_block_search(const uint8_t *block, uint64_t len, const uint8_t *key, uint64_t key_len,
+                                uint32_t *cell) {
+    if (len > SEB_BLOCK_BYTES)
+        return fail(SEB_ERR_INVALID, "seb_block_search: %llu bytes > the 4096 readBlock returns", (unsigned long long)len);
+    if (seb::block_search(block, len, key, key_len, cell) != 0)
+        return fail(SEB_ERR_INVALID, "seb_block_search: null argument");
+    return SEB_OK;
+}
+
+extern "C" int seb_blocks_dedup(const uint64_t *files, const uint64_t *blocks, uint64_t cells, uint32_t *bid,
+                                uint64_t *uniq_files, uint64_t *uniq_blocks, uint64_t uniq_cap, uint64_t *num_uniq) {
+    switch (seb::blocks_dedup(files, blocks, cells, bid, uniq_files, uniq_blocks, uniq_cap, num_uniq)) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_RANGE, "seb_blocks_dedup: %llu distinct blocks > uniq_cap %llu; retry with *num_uniq",
+                    (unsigned long long)*num_uniq, (unsigned long long)uniq_cap);
+    case -3:
+        return fail(SEB_ERR_NOMEM, "seb_blocks_dedup: out of host memory");
+    case -4:
+        return fail(SEB_ERR_INVALID, "seb_blocks_dedup: more than 2^32 - 1 distinct blocks");
+    default:
+        return fail(SEB_ERR_INVALID, "seb_blocks_dedup: null argument");
+    }
+}
+
+static int check_search_args(const seb_keys *keys, const void *bid, uint32_t cap, const uint8_t *pool, const void *blen,
+                             uint32_t num_blocks, const char *who) {
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    if (cap == 0) return fail(SEB_ERR_INVALID, "%s: cap 0", who);
+    if (!bid || (num_blocks && (!pool || !blen))) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_search_blocks(const seb_keys *keys, const uint32_t *bid, uint32_t cap, const uint8_t *pool,
+                                     const uint16_t *blen, uint32_t num_blocks, uint32_t *cells, void *stream) {
+    const char *who = "seb_dev_search_blocks";
+    enter();
+    int rc;
+    if (!pool || !blen || !cells) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if ((rc = check_search_args(keys, bid, cap, pool, blen, num_blocks, who))) return rc;
+    if ((uintptr_t)pool & 15) return fail(SEB_ERR_INVALID, "%s: the block pool is not 16-byte aligned", who);
+    if (keys->n == 0) return SEB_OK;
+    HIP_OR_FAIL(launch_search_blocks(key_batch(keys), bid, cap, pool, blen, num_blocks, cells, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_resolve_rows(const uint32_t *cells, const uint32_t *bid, uint64_t n, uint32_t cap,
+                                    uint8_t *status, uint16_t *col, uint64_t *vloc, uint32_t *vlen, void *stream) {
+    const char *who = "seb_dev_resolve_rows";
+    enter();
+    if (!cells || !bid || !status) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if (cap == 0) return fail(SEB_ERR_INVALID, "%s: cap 0", who);
+    if (n == 0) return SEB_OK;
+    HIP_OR_FAIL(launch_resolve_rows(cells, bid, n, cap, status, col, vloc, vlen, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+// Host buffers through the context: the pool and blen go up once, then a chunk of keys at a time on the
+// compute stream (copy in, search, resolve, copy out), as seb_registry_locate does.
+extern "C" int seb_search_blocks(seb_ctx *c, const seb_keys *kb, const uint32_t *bid, uint32_t cap,
+                                 const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, uint8_t *status,
+                                 uint16_t *col, uint64_t *vloc, uint32_t *vlen, uint32_t *cells) {
+    const char *who = "seb_search_blocks";
+    WsCall ws_call;
+    int rc;
+    if (!c) return fail(SEB_ERR_INVALID, "%s: null ctx", who);
+    if ((rc = check_search_args(kb, bid, cap, pool, blen, num_blocks, who)) || (rc = validate_offsets(kb, who))) return rc;
+    if (!status && kb->n) return fail(SEB_ERR_INVALID, "%s: null status", who);
+    if (kb->n == 0) return SEB_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OR_FAIL(hipSetDevice(c->device));
+    const uint64_t pool_bytes = (uint64_t)num_blocks * SEB_BLOCK_BYTES;
+    if ((rc = c->sb_pool.reserve(std::max<uint64_t>(pool_bytes, 16))) ||
+        (rc = c->sb_blen.reserve(std::max<uint64_t>(2ull * num_blocks, 16))))
+        return rc;
+    if (num_blocks) {
+        HIP_OR_FAIL(hipMemcpyAsync(c->sb_pool.p, pool, pool_bytes, hipMemcpyHostToDevice, c->s_comp));
+        HIP_OR_FAIL(hipMemcpyAsync(c->sb_blen.p, blen, 2ull * num_blocks, hipMemcpyHostToDevice, c->s_comp));
+    }
+    return chunks_serial(c, kb, [&](const KeyBatch &dk, const Chunk &ch) -> int {
+        const uint64_t n = dk.n, ncell = n * (uint64_t)cap;
+        // per key: vloc u64, vlen u32, col u16, status u8, each array 16-B aligned
+        const uint64_t o_vlen = (8 * n + 15) & ~15ull, o_col = (o_vlen + 4 * n + 15) & ~15ull,
+                       o_st = (o_col + 2 * n + 15) & ~15ull;
+        if ((rc = c->sb_bid.reserve(ncell * 4)) || (rc = c->sb_cells.reserve(ncell * 4)) ||
+            (rc = c->sb_out.reserve(o_st + n)))
+            return rc;
+        uint8_t *o = (uint8_t *)c->sb_out.p;
+        HIP_OR_FAIL(hipMemcpyAsync(c->sb_bid.p, bid + ch.i0 * cap, ncell * 4, hipMemcpyHostToDevice, c->s_comp));
+        HIP_OR_FAIL(launch_search_blocks(dk, (const uint32_t *)c->sb_bid.p, cap, (const uint8_t *)c->sb_pool.p,
+                                         (const uint16_t *)c->sb_blen.p, num_blocks, (uint32_t *)c->sb_cells.p,
+                                         c->s_comp));
+        HIP_OR_FAIL(launch_resolve_rows((const uint32_t *)c->sb_cells.p, (const uint32_t *)c->sb_bid.p, n, cap, o + o_st,
+                                        (uint16_t *)(o + o_col), (uint64_t *)o, (uint32_t *)(o + o_vlen), c->s_comp));
+        HIP_OR_FAIL(hipMemcpyAsync(status + ch.i0, o + o_st, n, hipMemcpyDeviceToHost, c->s_comp));
+        if (col) HIP_OR_FAIL(hipMemcpyAsync(col + ch.i0, o + o_col, 2 * n, hipMemcpyDeviceToHost, c->s_comp));
+        if (vloc) HIP_OR_FAIL(hipMemcpyAsync(vloc + ch.i0, o, 8 * n, hipMemcpyDeviceToHost, c->s_comp));
+        if (vlen) HIP_OR_FAIL(hipMemcpyAsync(vlen + ch.i0, o + o_vlen, 4 * n, hipMemcpyDeviceToHost, c->s_comp));
+        if (cells)
+            HIP_OR_FAIL(hipMemcpyAsync(cells + ch.i0 * cap, c->sb_cells.p, ncell * 4, hipMemcpyDeviceToHost, c->s_comp));
+        return SEB_OK;
+    });
+}
+
+// ------------------------------------------------ batched SSTable builder (lsm/sstable_builder.go)
+
+static_assert(sizeof(seb_sst_sizes) == sizeof(seb::SstSizes) && sizeof(seb_sst_sizes) == 40, "seb_sst_sizes layout");
+
+static int sst_host_rc(int rc, const seb_sst_sizes *sz, const char *who) {
+    switch (rc) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_INVALID, "%s: a key or a value of 2^32 bytes or more, or offsets that decrease", who);
+    case -3:
+        return fail(SEB_ERR_RANGE, "%s: a capacity is below its section (data %llu, index %llu, metadata %llu bytes)", who,
+                    (unsigned long long)sz->data_bytes, (unsigned long long)sz->index_bytes,
+                    (unsigned long long)sz->meta_bytes);
+    default:
+        return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    }
+}
+
+static seb::SstKeys sst_keys(const seb_keys *kb) { return seb::SstKeys{kb->data, kb->offsets, kb->n, kb->stride}; }
+
+extern "C" int seb_sst_plan(const seb_keys *keys, const uint64_t *val_off, seb_sst_sizes *sizes) {
+    int rc;
+    if ((rc = check_keys(keys, "seb_sst_plan"))) return rc;
+    return sst_host_rc(seb::sst_walk(sst_keys(keys), nullptr, val_off, nullptr, nullptr, (seb::SstSizes *)sizes), sizes,
+                       "seb_sst_plan");
+}
+
+extern "C" int seb_sst_encode(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                              uint8_t *data, uint64_t data_cap, uint8_t *index, uint64_t index_cap, uint8_t *meta,
+                              uint64_t meta_cap, seb_sst_sizes *sizes) {
+    int rc;
+    if ((rc = check_keys(keys, "seb_sst_encode"))) return rc;
+    seb_sst_sizes local;
+    if (!sizes) sizes = &local;
+    const seb::SstOut out{data, index, meta, data_cap, index_cap, meta_cap};
+    return sst_host_rc(seb::sst_walk(sst_keys(keys), vals, val_off, deleted, &out, (seb::SstSizes *)sizes), sizes,
+                       "seb_sst_encode");
+}
+
+extern "C" int seb_sst_footer(uint64_t index_offset, uint64_t bloom_offset, uint64_t metadata_offset, uint8_t *out28) {
+    if (!out28) return fail(SEB_ERR_INVALID, "seb_sst_footer: null output");
+    seb::sst_footer(index_offset, bloom_offset, metadata_offset, out28);
+    return SEB_OK;
+}
+
+extern "C" uint64_t seb_dev_sst_workspace_size(uint64_t n, uint32_t num_files) {
+    return n == 0 || n >= (1ull << 32) ? 0 : sst_ws_layout(n, num_files).bytes;
+}
+
+static int check_sst_dev_args(const seb_keys *keys, const uint64_t *val_off, const uint64_t *file_begin,
+                              uint32_t num_files, const void *ws, uint64_t ws_bytes, const char *who) {
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    if (!file_begin || num_files == 0) return fail(SEB_ERR_INVALID, "%s: no files", who);
+    if (file_begin[0] != 0 || file_begin[num_files] != keys->n)
+        return fail(SEB_ERR_INVALID, "%s: file_begin must run from 0 to n = %llu", who, (unsigned long long)keys->n);
+    for (uint32_t f = 0; f < num_files; ++f)
+        if (file_begin[f + 1] < file_begin[f]) return fail(SEB_ERR_INVALID, "%s: file_begin decreases at %u", who, f);
+    if (keys->n == 0) return SEB_OK;
+    if (keys->n >= (1ull << 32)) return fail(SEB_ERR_INVALID, "%s: n >= 2^32", who);
+    if (!val_off) return fail(SEB_ERR_INVALID, "%s: null val_off", who);
+    if (!ws || ((uintptr_t)ws & 15)) return fail(SEB_ERR_INVALID, "%s: the workspace is null or not 16-byte aligned", who);
+    const uint64_t want = sst_ws_layout(keys->n, num_files).bytes;
+    if (ws_bytes < want)
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes", who, (unsigned long long)ws_bytes,
+                    (unsigned long long)want);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_sst_plan(const seb_keys *keys, const uint64_t *val_off, const uint64_t *file_begin,
+                                uint32_t num_files, void *ws, uint64_t ws_bytes, seb_sst_sizes *sizes, void *stream) {
+    const char *who = "seb_dev_sst_plan";
+    enter();
+    int rc;
+    if ((rc = check_sst_dev_args(keys, val_off, file_begin, num_files, ws, ws_bytes, who))) return rc;
+    if (!sizes) return fail(SEB_ERR_INVALID, "%s: null sizes", who);
+    if (keys->n == 0) {  // every file is empty: a 4-byte index and 8 bytes of metadata each
+        for (uint32_t f = 0; f < num_files; ++f) sizes[f] = seb_sst_sizes{0, 0, 4, 8, 0};
+        return SEB_OK;
+    }
+    HIP_OR_FAIL(launch_sst_plan(key_batch(keys), val_off, file_begin, num_files, ws, sizes, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_sst_encode(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off,
+                                  const uint8_t *deleted, const uint64_t *file_begin, uint32_t num_files,
+                                  const seb_sst_sizes *sizes, const void *ws, uint64_t ws_bytes, uint8_t *data,
+                                  uint16_t *blen, uint8_t *index, uint8_t *meta, void *stream) {
+    const char *who = "seb_dev_sst_encode";
+    enter();
+    int rc;
+    if ((rc = check_sst_dev_args(keys, val_off, file_begin, num_files, ws, ws_bytes, who))) return rc;
+    if (!sizes) return fail(SEB_ERR_INVALID, "%s: null sizes", who);
+    if (keys->n == 0) return SEB_OK;
+    uint64_t blocks = 0, index_total = 0, meta_total = 0;
+    for (uint32_t f = 0; f < num_files; ++f) {
+        if (sizes[f].oversize_entries)
+            return fail(SEB_ERR_RANGE, "%s: file %u has %llu oversized entries (a block longer than 4096 bytes): use "
+                        "seb_sst_encode for it", who, f, (unsigned long long)sizes[f].oversize_entries);
+        if (sizes[f].data_bytes != sizes[f].num_blocks * SEB_BLOCK_BYTES)
+            return fail(SEB_ERR_INVALID, "%s: file %u: sizes are not a plan's", who, f);
+        blocks += sizes[f].num_blocks;
+        index_total += sizes[f].index_bytes;
+        meta_total += sizes[f].meta_bytes;
+    }
+    if (blocks > keys->n) return fail(SEB_ERR_INVALID, "%s: sizes are not a plan's: more blocks than entries", who);
+    if (!index || !meta || (blocks && !data)) return fail(SEB_ERR_INVALID, "%s: null output", who);
+    if ((uintptr_t)data & 15) return fail(SEB_ERR_INVALID, "%s: the data section is not 16-byte aligned", who);
+    HIP_OR_FAIL(launch_sst_encode(key_batch(keys), vals, val_off, deleted, num_files, ws, blocks, index_total, meta_total,
+                                  data, blen, index, meta, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+// One file from host memory: the run goes up in one piece, the plan and the encode run on the compute
+// stream, the filter is built from the keys already on the device, and the sections come back into
+// `out` at their places.  A file with an oversized entry (or no entry) is encoded by the host half.
+extern "C" int seb_sst_build(seb_ctx *c, const seb_keys *kb, const uint8_t *vals, const uint64_t *val_off,
+                             const uint8_t *deleted, int64_t expected_keys, uint8_t *out, uint64_t cap, uint64_t *need) {
+    const char *who = "seb_sst_build";
+    int rc;
+    if (!c) return fail(SEB_ERR_INVALID, "%s: null ctx", who);
+    if ((rc = check_keys(kb, who))) return rc;
+    const uint64_t n = kb->n;
+    if (n && expected_keys == 0)
+        return fail(SEB_ERR_INVALID, "%s: expected_keys == 0 with %llu entries (the reference's Add panics: integer "
+                    "divide by zero)", who, (unsigned long long)n);
+    uint64_t m = 0;
+    uint32_t k = 0;
+    if ((rc = seb_params(expected_keys, 0.01, &m, &k))) return rc;
+    seb_sst_sizes sz;
+    if ((rc = seb_sst_plan(kb, val_off, &sz))) return rc;
+    const uint64_t nb = seb_num_bytes(m);
+    const uint64_t o_index = sz.data_bytes, o_meta = o_index + sz.index_bytes, o_bloom = o_meta + sz.meta_bytes,
+                   o_foot = o_bloom + 12 + nb, total = o_foot + SEB_SST_FOOTER_BYTES;
+    if (need) *need = total;
+    if (cap < total)
+        return fail(SEB_ERR_RANGE, "%s: cap %llu < the file image's %llu bytes; retry with *need", who,
+                    (unsigned long long)cap, (unsigned long long)total);
+    if (!out) return fail(SEB_ERR_INVALID, "%s: null out", who);
+    memcpy(out + o_bloom, &m, 8);  // Encode(): [numBits u64][numHashes u32][bits]
+    memcpy(out + o_bloom + 8, &k, 4);
+    seb::sst_footer(o_index, o_bloom, o_meta, out + o_foot);
+    const bool on_host = n == 0 || sz.oversize_entries || n >= (1ull << 32);
+    if (on_host) {
+        rc = seb_sst_encode(kb, vals, val_off, deleted, out, sz.data_bytes, out + o_index, sz.index_bytes, out + o_meta,
+                            sz.meta_bytes, nullptr);
+        if (rc) return rc;
+        if (n == 0) {
+            memset(out + o_bloom + 12, 0, nb);
+            return SEB_OK;
+        }
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OR_FAIL(hipSetDevice(c->device));
+    hipStream_t s = c->s_comp;
+    // the filter: NewBloomFilter(expected_keys, 0.01) + Add per key
+    const uint64_t wb = seb_words_bytes(m);
+    if ((rc = c->words.reserve(wb))) return rc;
+    uint32_t *dw = (uint32_t *)c->words.p;
+    HIP_OR_FAIL(hipMemsetAsync(dw, 0, wb, s));
+    if ((rc = build_device_from_host(c, kb, dw, mod_arg(m, k)))) return rc;
+    HIP_OR_FAIL(hipMemcpyAsync(out + o_bloom + 12, dw, nb, hipMemcpyDeviceToHost, s));
+    if (on_host) {
+        HIP_OR_FAIL(hipStreamSynchronize(s));
+        return SEB_OK;
+    }
+    // the run on the device: key bytes, key offsets, value bytes, value offsets, deleted bytes
+    const uint64_t k0 = kb->offsets ? kb->offsets[0] : 0, k1 = kb->offsets ? kb->offsets[n] : n * (uint64_t)kb->stride;
+    const uint64_t v0 = val_off[0], v1 = val_off[n];
+    if ((v1 - v0) && !vals) return fail(SEB_ERR_INVALID, "%s: null vals", who);
+    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t a_keys = 0, a_koff = a_keys + up(k1 - k0), a_vals = a_koff + up(kb->offsets ? 8 * (n + 1) : 0),
+                   a_voff = a_vals + up(v1 - v0), a_del = a_voff + up(8 * (n + 1)), in_bytes = a_del + up(n);
+    const uint64_t ws_bytes = sst_ws_layout(n, 1).bytes;
+    const uint64_t a_index = up(sz.data_bytes), a_metao = a_index + up(sz.index_bytes), out_bytes = a_metao + up(sz.meta_bytes);
+    if ((rc = c->sst_in.reserve(in_bytes)) || (rc = c->sst_ws.reserve(ws_bytes, true)) || (rc = c->sst_out.reserve(out_bytes)))
+        return rc;
+    uint8_t *in = (uint8_t *)c->sst_in.p, *dout = (uint8_t *)c->sst_out.p;
+    if (k1 - k0) HIP_OR_FAIL(hipMemcpyAsync(in + a_keys, kb->data + k0, k1 - k0, hipMemcpyHostToDevice, s));
+    if (kb->offsets) HIP_OR_FAIL(hipMemcpyAsync(in + a_koff, kb->offsets, 8 * (n + 1), hipMemcpyHostToDevice, s));
+    if (v1 - v0) HIP_OR_FAIL(hipMemcpyAsync(in + a_vals, vals + v0, v1 - v0, hipMemcpyHostToDevice, s));
+    HIP_OR_FAIL(hipMemcpyAsync(in + a_voff, val_off, 8 * (n + 1), hipMemcpyHostToDevice, s));
+    if (deleted) HIP_OR_FAIL(hipMemcpyAsync(in + a_del, deleted, n, hipMemcpyHostToDevice, s));
+    KeyBatch dk{};  // offsets stay absolute: the data pointers are moved back by the first offset
+    dk.data = in + a_keys - k0;
+    dk.offsets = kb->offsets ? (const uint64_t *)(in + a_koff) : nullptr;
+    dk.n = n;
+    dk.stride = kb->stride;
+    const uint64_t fbeg[2] = {0, n};
+    seb_sst_sizes dsz;
+    HIP_OR_FAIL(launch_sst_plan(dk, (const uint64_t *)(in + a_voff), fbeg, 1, c->sst_ws.p, &dsz, s));
+    if (memcmp(&dsz, &sz, sizeof sz) != 0)
+        return fail(SEB_ERR_INTERNAL, "%s: the device plan (%llu blocks, %llu index bytes) differs from the host's (%llu, %llu)",
+                    who, (unsigned long long)dsz.num_blocks, (unsigned long long)dsz.index_bytes,
+                    (unsigned long long)sz.num_blocks, (unsigned long long)sz.index_bytes);
+    HIP_OR_FAIL(launch_sst_encode(dk, in + a_vals - v0, (const uint64_t *)(in + a_voff),
+                                  deleted ? in + a_del : nullptr, 1, c->sst_ws.p, sz.num_blocks, sz.index_bytes,
+                                  sz.meta_bytes, dout, nullptr, dout + a_index, dout + a_metao, s));
+    HIP_OR_FAIL(hipMemcpyAsync(out, dout, sz.data_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipMemcpyAsync(out + o_index, dout + a_index, sz.index_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipMemcpyAsync(out + o_meta, dout + a_metao, sz.meta_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipStreamSynchronize(s));
+    return SEB_OK;
+}

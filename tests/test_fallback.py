@@ -3,7 +3,7 @@
 The Go API has no error returns (lsm/bloom.go:19-41,70-77,96-102 never fail on valid input), so
 the Go API mirror (seb_filter_*, the cgo shim's calls) must keep working when its device path
 fails: a build or batched probe that gets SEB_ERR_DEVICE / SEB_ERR_NOMEM is done on the filter's
-host copy (product code in csrc/seb_host.cpp, not the oracle) and counted by seb_fallback_count().
+host copy (product code in csrc/seb_filter.cpp, not the oracle) and counted by seb_fallback_count().
 
 The device error is forced with the test-only option fault_inject (and, in this container, also
 happens for real: there is no GPU).  Each case runs in a child process, so the fallbacks it

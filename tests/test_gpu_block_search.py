@@ -197,6 +197,42 @@ def test_row_shapes(seb, torch_cuda, table):
                                      cells.data_ptr(), None) == 0
 
 
+def test_host_form_chunked(seb, torch_cuda, table, monkeypatch):
+    """seb_search_blocks past its first chunk of keys: with SEB_CHUNK_BYTES = 4096 a chunk is 256
+    16-byte keys, so the batches are no chunk, one key, one full chunk, a one-key second chunk, and
+    four chunks with a one-key tail.  Cells against search_block_ref, rows against lsm_get_ref."""
+    monkeypatch.setenv("SEB_CHUNK_BYTES", "4096")
+    ctx = seb.Ctx(0)
+    rng = np.random.default_rng(17)
+    images = table
+    nb, cap, top = len(images), 3, 769
+    pool, blen = make_pool(images)
+    ids = np.array(list(range(nb)) * 3 + [NO_ID] * 4 + [nb, 2**31], np.uint32)
+    probes = [kg.key16_bytes(int(i)) for i in rng.integers(0, 920, top)]
+    bid = ids[rng.integers(0, len(ids), (top, cap))]
+    memo = {}
+    want = np.zeros((top, cap), np.uint32)
+    rows = []
+    for i, key in enumerate(probes):
+        for j, b in enumerate(bid[i].tolist()):
+            if b < nb:
+                if (b, key) not in memo:
+                    memo[(b, key)] = br.search_block_ref(images[b], key)
+                want[i, j] = memo[(b, key)]
+        st, wc, c = br.lsm_get_ref(want[i].tolist())
+        found = st == br.GET_FOUND
+        rows.append((st, wc, int(bid[i, wc]) * 4096 + ((c >> 13) & 0x1FFF) if found else 0, c & 0x1FFF if found else 0))
+    rows = np.array(rows, np.uint64)
+    assert {br.GET_MISS, br.GET_FOUND} <= set(rows[:, 0].tolist()) and (want >> 28 == br.NONE).any()
+    data = np.frombuffer(b"".join(probes), np.uint8).reshape(top, 16)
+    for n in (0, 1, 256, 257, top):
+        st, col, vloc, vlen, cells = ctx.search_blocks(data[:n], bid[:n], pool, blen, want_cells=True)
+        assert np.array_equal(cells, want[:n]), n
+        for got, ref in zip((st, col, vloc, vlen), rows[:n].T.reshape(4, n)):
+            assert np.array_equal(got.astype(np.uint64), ref), n
+    ctx.close()
+
+
 def test_resolve(seb, torch_cuda):
     """Rows of every ordering of MISS / TOMBSTONE / FOUND / TRUNC / NONE over cap 1..5 against
     lsm_get_ref; null optional outputs; the orderings the issue names."""

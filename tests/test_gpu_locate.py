@@ -216,12 +216,9 @@ def lsm_walk(files, key: bytes):
     return [f for f in visit if oc.probe(f["bits"], f["m"], f["k"], kb, 1, stride=len(key))[0]]
 
 
-def test_end_to_end_read_plan(seb, torch_cuda):
-    """A 3-level registry (overlapping L0 files, a disjoint L1, an L2) with each file's index being
-    every 8th key: multiget_list_dev then locate_dev equals LSM.Get's walk followed by
-    SSTable.Get's index step, and multiget_blocks returns the same pairs as file numbers."""
-    torch = torch_cuda
-    rng = np.random.default_rng(21)
+def three_level_registry(seb, rng):
+    """(registry, files): 3 overlapping L0 files, a disjoint L1 of 4, an L2 of 3 put out of order;
+    each file's index is every 8th key."""
     universe = np.arange(0, 6000, 2)
     reg = seb.Registry(0)
     files = []
@@ -241,15 +238,32 @@ def test_end_to_end_read_plan(seb, torch_cuda):
         add(1000 + j, 1, part)
     for j, part in reversed(list(enumerate(np.array_split(universe, 3)))):
         add(2000 + j, 2, part)
-    probes = [kg.key16_bytes(int(i)) for i in rng.integers(0, 6100, 1500)] + [files[0]["min"], files[-1]["max"]]
-    n, cap = len(probes), reg.max_candidates()
-    assert cap == 5
+    return reg, files
+
+
+def read_plan_ref(files, probes, cap):
+    """(file numbers, slots, block offsets), each (n, cap): LSM.Get's walk, then SSTable.Get's index step."""
+    n = len(probes)
     want_files = np.full((n, cap), NO_BLOCK, np.uint64)
     want_slots = np.full((n, cap), PAD, np.uint16)
     want_blocks = np.full((n, cap), NO_BLOCK, np.uint64)
     for i, p in enumerate(probes):
         for j, f in enumerate(lsm_walk(files, p)):
             want_files[i, j], want_slots[i, j], want_blocks[i, j] = f["file"], f["slot"], ref_block(f["entries"], p)
+    return want_files, want_slots, want_blocks
+
+
+def test_end_to_end_read_plan(seb, torch_cuda):
+    """A 3-level registry (overlapping L0 files, a disjoint L1, an L2) with each file's index being
+    every 8th key: multiget_list_dev then locate_dev equals LSM.Get's walk followed by
+    SSTable.Get's index step, and multiget_blocks returns the same pairs as file numbers."""
+    torch = torch_cuda
+    rng = np.random.default_rng(21)
+    reg, files = three_level_registry(seb, rng)
+    probes = [kg.key16_bytes(int(i)) for i in rng.integers(0, 6100, 1500)] + [files[0]["min"], files[-1]["max"]]
+    n, cap = len(probes), reg.max_candidates()
+    assert cap == 5
+    want_files, want_slots, want_blocks = read_plan_ref(files, probes, cap)
     assert (want_blocks != NO_BLOCK).sum() > n // 2  # about every second probe is present in two levels
     dk = seb.dev_keys(torch.from_numpy(np.frombuffer(b"".join(probes), np.uint8).copy()).cuda(), n=n, stride=16)
     rows = torch.zeros(n * cap, dtype=torch.int16, device="cuda")
@@ -269,6 +283,44 @@ def test_end_to_end_read_plan(seb, torch_cuda):
     assert got_files.shape == (n, cap)
     assert np.array_equal(got_files, want_files) and np.array_equal(got_blocks, want_blocks)
     assert np.array_equal(got_files, reg.multiget_files(hk))
+    reg.close()
+
+
+def test_host_forms_chunked(seb, torch_cuda, monkeypatch):
+    """The host-pointer forms past their first chunk.  The registry's context reads SEB_CHUNK_BYTES
+    when the first host call creates it: 4096 bytes are 256 16-byte keys, so the batches are no
+    chunk, one key, one full chunk, a one-key second chunk, and four chunks with a one-key tail."""
+    monkeypatch.setenv("SEB_CHUNK_BYTES", "4096")
+    rng = np.random.default_rng(23)
+    reg, files = three_level_registry(seb, rng)
+    cap = reg.max_candidates()
+    assert cap == 5
+    probes = [kg.key16_bytes(int(i)) for i in rng.integers(0, 6100, 767)] + [files[0]["min"], files[-1]["max"]]
+    want_files, want_slots, want_blocks = read_plan_ref(files, probes, cap)
+    want_mask = np.zeros(len(probes), np.uint64)
+    for j in range(cap):
+        live = want_slots[:, j] != PAD
+        want_mask[live] |= np.uint64(1) << want_slots[live, j].astype(np.uint64)
+    by_slot = {f["slot"]: f["entries"] for f in files}
+    mixed = want_slots.copy()  # locate's own rows: every slot, padding and a free id, whatever the filters say
+    mixed[::3] = np.array(sorted(by_slot)[:cap], np.uint16)
+    mixed[1::7, 1] = 4095
+    want_mixed = ref_rows(by_slot, probes, mixed)
+    assert (want_blocks != NO_BLOCK).sum() > len(probes) // 2
+    for n in (0, 1, 256, 257, 769):
+        hk = seb.as_keys(np.frombuffer(b"".join(probes[:n]), np.uint8).reshape(n, 16))
+        assert np.array_equal(reg.multiget(hk), want_mask[:n]), n
+        assert np.array_equal(reg.multiget_list(hk), want_slots[:n]), n
+        wide = reg.multiget_list(hk, cap=cap + 2)  # an odd row width
+        assert wide.shape == (n, cap + 2), n
+        assert np.array_equal(wide[:, :cap], want_slots[:n]) and (wide[:, cap:] == PAD).all(), n
+        got = reg.multiget_files(hk)
+        assert got.shape == (n, cap) and np.array_equal(got, want_files[:n]), n
+        assert np.array_equal(reg.locate(hk, want_slots[:n]), want_blocks[:n]), n
+        assert np.array_equal(reg.locate(hk, mixed[:n]), want_mixed[:n]), n
+        got_files, got_blocks = reg.multiget_blocks(hk)
+        assert got_files.shape == (n, cap), n
+        assert np.array_equal(got_files, want_files[:n]) and np.array_equal(got_blocks, want_blocks[:n]), n
     reg.close()
 
 

@@ -226,6 +226,46 @@ def test_host_api_chunked_pipeline(seb, monkeypatch, torch_cuda):
     c.close()
 
 
+# 4096-byte chunks of 16-byte keys hold 256: no chunk, one key, one full chunk, a one-key second
+# chunk, and four chunks (both buffers reused) with a one-key tail
+CHUNK_NS = (0, 1, 256, 257, 769)
+
+
+def test_host_probe_multi_chunked(seb, monkeypatch, torch_cuda):
+    """seb_probe_multi's chunk loop past its first iteration: 3 filters of different (m, k)."""
+    monkeypatch.setenv("SEB_CHUNK_BYTES", "4096")
+    c = seb.Ctx(0)
+    filters = []
+    for j, (cnt, p) in enumerate(((500, 0.01), (300, 0.001), (1000, 0.05))):
+        m, k = oc.params(cnt, p)
+        filters.append((oc.build(m, k, kg.key16(np.arange(j * 200, j * 200 + cnt)), cnt, stride=16), m, k))
+    assert len({(m, k) for _, m, k in filters}) == 3
+    keys = kg.key16(np.arange(max(CHUNK_NS)) * 2)
+    want = oc.probe_multi(filters, keys, len(keys), stride=16)
+    assert len(set(want.tolist())) >= 4
+    for n in CHUNK_NS:
+        assert np.array_equal(c.probe_multi(keys[:n], filters), want[:n]), n
+    c.close()
+
+
+def test_host_probe_chunked_long_key(seb, monkeypatch, torch_cuda):
+    """A variable-length batch with keys longer than the chunk budget: each gets a chunk of its own."""
+    monkeypatch.setenv("SEB_CHUNK_BYTES", "4096")
+    c = seb.Ctx(0)
+    keys = [b"key-%d" % i * (1 + i % 5) for i in range(600)]
+    keys[0] = b"first" * 1000
+    keys[301] = b"L" * 4097
+    keys.append(b"last" * 2000)
+    kb = seb.as_keys(keys)
+    n = len(keys)
+    m, k = oc.params(n, 0.01)
+    bits = oc.build(m, k, kb.data[: int(kb.offsets[n // 2])], n // 2, offsets=kb.offsets[: n // 2 + 1])
+    want = oc.probe(bits, m, k, kb.data, n, offsets=kb.offsets)
+    assert want[0] == 1 and want[: n // 2].all() and not want[n // 2:].all()
+    assert np.array_equal(c.probe(kb, bits, m, k), want)
+    c.close()
+
+
 # --------------------------------------------------------- device-resident API --------------
 
 @pytest.fixture(params=[1, 2, 3, 4], ids=["atomic", "bucketed", "lds", "images"])

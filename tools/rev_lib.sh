@@ -1,21 +1,16 @@
 #!/bin/bash
 # Build libseb_bloom.so from the product sources of a git revision into tools/ab_lib/NAME/ (CPU,
 # here), for an A/B against the in-tree library on the box (SEB_LIB_PATH, tools/gpu_ab_lib.sh).
+# The revision's own Makefile builds whatever files that revision has.
 #   tools/rev_lib.sh NAME [REV]      (REV defaults to HEAD)
 set -e
 NAME=$1; REV=${2:-HEAD}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/tools/ab_lib/$NAME
 SRC=$OUT/src
-rm -rf "$SRC" && mkdir -p "$OUT/obj" "$SRC/storage-engines_amd/csrc" "$SRC/include"
+# git archive gives the sources the commit's time, so objects left by an earlier build under this
+# NAME would look up to date: they go first
+rm -rf "$SRC" "$OUT/obj" "$OUT/libseb_bloom.so" && mkdir -p "$SRC"
 (cd "$ROOT" && git archive "$REV" storage-engines_amd/csrc include) | tar -x -C "$SRC"
-C=$SRC/storage-engines_amd/csrc
-FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
-for f in $(cd $C && ls *.hip | sed "s/\.hip$//"); do
-  /opt/rocm/bin/hipcc $FL -c $C/$f.hip -o $OUT/obj/$f.o &
-done
-/opt/rocm/bin/hipcc $FL -c $C/seb_host.cpp -o $OUT/obj/seb_host.o &
-g++ -O2 -std=c++17 -fPIC -ffp-contract=off -c $C/seb_sizing.cpp -o $OUT/obj/seb_sizing.o &
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libseb_bloom.so $OUT/obj/*.o -Wl,-rpath,/opt/rocm/lib
+make -s -j8 -C "$SRC/storage-engines_amd/csrc" OUTDIR="$OUT"
 echo "$OUT/libseb_bloom.so"
