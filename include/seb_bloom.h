@@ -495,6 +495,93 @@ int seb_dev_sst_encode(const seb_keys *keys, const uint8_t *vals, const uint64_t
 int seb_sst_build(seb_ctx *ctx, const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off,
                   const uint8_t *deleted, int64_t expected_keys, uint8_t *out, uint64_t cap, uint64_t *need);
 
+/* ------------- batched compaction merge: k sorted runs of a block pool into one run for the builder ---- */
+/* What mergeFiles computes before its builder (lsm/compaction.go:226-333): every input file's data blocks are
+ * parsed (SSTableIterator.loadBlock, :69-124), the entries go through a k-way merge by key, duplicates are
+ * skipped, and at targetLevel == 4 tombstones are dropped.  Input: the data sections of the input files as
+ * runs of a block pool in the block search's layout (block b at pool + b * 4096, blen[b] bytes, a larger blen
+ * read as 4096, base 16-byte aligned); run r is blocks [run_begin[r], run_begin[r+1]), run_begin a HOST array
+ * of num_runs + 1 non-decreasing entries from 0 to num_blocks; a run's entries are its blocks' entries in
+ * block order.  Output: one sorted run in the builder's input layout above.
+ *
+ * The decode is loadBlock's walk, bit-exact: fewer than 4 bytes: no entries.  From off = 4, for i < numEntries:
+ * off + 9 > len ends the block; keySize, valueSize, deleted = (byte == 1) are read; off + 9 + keySize +
+ * valueSize > len (64-bit sums) ends the block; both ends are silent (a break, not searchBlock's error).  An
+ * overstated numEntries therefore walks into the zero padding as empty-key entries; a deleted byte of 2 or 255
+ * is "not deleted".  A block yields at most 454 entries.
+ *
+ * The merge orders by key alone (every entry's Sequence is 0, :119): one entry per distinct key comes out, in
+ * ascending Go string order; with SEB_MERGE_DROP_TOMBSTONES a surviving tombstone is then dropped (it still
+ * shadows the older entries of its key: they do not resurface).
+ *
+ * ONE DEPARTURE FROM THE REFERENCE.  Of several entries with one key, the reference keeps whichever
+ * container/heap's array order leaves for last (merge([[a],[a]]) keeps input 1; over random inputs the lowest,
+ * the highest and a middle holder all occur): an accident of the heap, not a rule.  Here the entry of the
+ * LOWEST-NUMBERED RUN survives; the caller orders the runs.  In mergeFiles' allFiles order (the L0 files, then
+ * the overlapping files of the next level, :180,216) that is the file LSM.Get visits first (lsm.go:168-198).
+ * The key sequence and the decode are bit-exact, and when no key occurs in two runs so is the whole output.
+ *
+ * Every run must be STRICTLY INCREASING in Go string order (true of anything a memtable flush or an earlier
+ * merge wrote; the reference does not check it, and its output on such input is again heap-dependent).  Both
+ * halves check it: the plan returns SEB_ERR_INVALID and seb_last_error names the lowest-numbered offending run
+ * and its first entry that is not above its predecessor ("run R entry E", E counted inside the run).  Nothing
+ * is read out of bounds on any input.  An overstated numEntries that reaches the padding ends as this error
+ * unless the run's only key is the empty key.
+ *
+ * Output entry o: key keys[key_off[o], key_off[o+1]), value vals[val_off[o], val_off[o+1]), deleted[o] = 1
+ * or 0; key_off[0] = val_off[0] = 0, entries_out + 1 offsets each: the seb_keys offset form + vals / val_off /
+ * deleted that seb_dev_sst_plan, seb_dev_sst_encode and seb_dev_build_many take (file_begin[f] =
+ * min(f * 100000, entries_out) is mergeFiles' file split, :253,301).  Nothing outside the sizes the plan
+ * returned is written.  Limits: entries_in < 2^32, num_blocks < 2^32, num_runs <= SEB_MERGE_MAX_RUNS.
+ * num_runs == 0, an empty pool, runs of 0 blocks and blocks of 0 entries are valid. */
+#define SEB_MERGE_DROP_TOMBSTONES 1u /* targetLevel == 4 */
+#define SEB_MERGE_MAX_RUNS 1048576u
+typedef struct seb_merge_sizes {
+    uint64_t entries_in, entries_out; /* decoded / surviving */
+    uint64_t key_bytes, val_bytes;    /* of the survivors */
+    uint64_t shadowed, dropped;       /* lost to a lower-numbered run / tombstones dropped */
+} seb_merge_sizes;
+
+/* Host only.  seb_block_entries: the decode above for one block image; entry_off[i] = the offset of entry i's
+ * 9-byte header, *count = the entries found.  len > 4096: SEB_ERR_INVALID; cap < *count: SEB_ERR_RANGE with
+ * *count filled (the first cap offsets are written).  seb_merge_plan sizes the output; seb_merge_emit (`sizes`
+ * as the plan returned them; anything else: SEB_ERR_INVALID) writes it.  They are the reference for the device
+ * form and what a caller without a GPU uses. */
+int seb_block_entries(const uint8_t *block, uint64_t len, uint16_t *entry_off, uint32_t cap, uint32_t *count);
+int seb_merge_plan(const uint8_t *pool, const uint16_t *blen, const uint64_t *run_begin, uint32_t num_runs,
+                   uint32_t flags, seb_merge_sizes *sizes);
+int seb_merge_emit(const uint8_t *pool, const uint16_t *blen, const uint64_t *run_begin, uint32_t num_runs,
+                   uint32_t flags, uint8_t *keys, uint64_t *key_off, uint8_t *vals, uint64_t *val_off,
+                   uint8_t *deleted, const seb_merge_sizes *sizes);
+
+/* Device pointers (run_begin, run_entries and sizes are HOST memory).
+ * seb_dev_merge_count: block_entries[b] (device, num_blocks u16) = block b's entry count; SYNCHRONISES and
+ * fills run_entries[num_runs] (nullable), whose sum is the `entries` of the workspace size.
+ * seb_dev_merge_plan (block_entries as count left them; workspace: seb_dev_merge_workspace_size bytes of device
+ * memory, 16-byte aligned, opaque, too small: SEB_ERR_INVALID) decodes, checks the runs' order, merges, marks
+ * the survivors, SYNCHRONISES and fills *sizes, so the caller can allocate the outputs.
+ * seb_dev_merge_emit (not synchronised; the same pool and workspace, untouched in between; `sizes` as the plan
+ * returned them) writes the five output arrays; keys and vals may have any byte alignment.  Before it launches
+ * it reads the workspace's 128-byte header back (so it waits for what the stream already holds; nothing, right
+ * after the plan): a workspace that does not hold the plan that returned `sizes` is SEB_ERR_INVALID and nothing
+ * is written.  Nothing is launched when entries_in == 0. */
+int seb_dev_merge_count(const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, const uint64_t *run_begin,
+                        uint32_t num_runs, uint16_t *block_entries, uint64_t *run_entries, void *stream);
+uint64_t seb_dev_merge_workspace_size(uint64_t entries, uint32_t num_blocks, uint32_t num_runs);
+int seb_dev_merge_plan(const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, const uint64_t *run_begin,
+                       uint32_t num_runs, const uint16_t *block_entries, uint32_t flags, void *workspace,
+                       uint64_t workspace_bytes, seb_merge_sizes *sizes, void *stream);
+int seb_dev_merge_emit(const uint8_t *pool, const seb_merge_sizes *sizes, const void *workspace,
+                       uint64_t workspace_bytes, uint8_t *keys, uint64_t *key_off, uint8_t *vals, uint64_t *val_off,
+                       uint8_t *deleted, void *stream);
+/* The host-buffer form on a context: pool (num_blocks * 4096 bytes), blen and the outputs in host memory;
+ * H2D, count, plan, emit, D2H; synchronous.  key_cap / val_cap bytes and entry_cap entries (key_off and val_off
+ * hold entry_cap + 1 offsets); a capacity below a size: SEB_ERR_RANGE with *sizes filled, so the caller can
+ * retry (the seb_sst_build convention). */
+int seb_merge(seb_ctx *ctx, const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, const uint64_t *run_begin,
+              uint32_t num_runs, uint32_t flags, uint8_t *keys, uint64_t key_cap, uint64_t *key_off, uint8_t *vals,
+              uint64_t val_cap, uint64_t *val_off, uint8_t *deleted, uint64_t entry_cap, seb_merge_sizes *sizes);
+
 /* ---------- hash-index shard routing + WAL record checksums (off the bloom path) ---- */
 /* shard[i] = FNV-1a32(key i) & ((1 << shard_bits) - 1), the reference's getShard
  * (hashindex/shard.go:47-52; 256 shards = shard_bits 8).  hash[i] (nullable) = the full FNV-1a32.

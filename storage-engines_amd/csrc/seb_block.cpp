@@ -1,7 +1,7 @@
 // seb_block.cpp — the host side of the batched data-block search: searchBlock's walk
 // (lsm/sstable.go:242-290) for one block image and one key, and the read-list builder; and the host
-// half of the batched SSTable builder (below).  No HIP dependency, so it compiles alone
-// (tools/sanitize/block_check.cpp, sst_check.cpp); the C ABI wrappers that set seb_last_error are in
+// half of the batched SSTable builder and of the batched compaction merge (below).  No HIP dependency, so it compiles alone
+// (tools/sanitize/block_check.cpp, sst_check.cpp, merge_check.cpp); the C ABI wrappers that set seb_last_error are in
 // seb_sstable.cpp.
 //
 //   numEntries := u32(block[0:4]); off := 4                              sstable.go:243-248
@@ -17,7 +17,9 @@
 #include <cstdint>
 #include <cstring>
 #include <new>
+#include <algorithm>
 #include <unordered_map>
+#include <vector>
 
 #include "seb_block.h"
 
@@ -203,6 +205,135 @@ void sst_footer(uint64_t index_offset, uint64_t bloom_offset, uint64_t metadata_
     put64(out28 + 8, bloom_offset);
     put64(out28 + 16, metadata_offset);
     put32(out28 + 24, 0x5354424Cu);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The host half of the batched compaction merge: SSTableIterator.loadBlock (lsm/compaction.go:69-124)
+// for one block image, and mergeFiles' loop (:226-333) over k sorted runs of a block pool.
+//
+//   loadBlock: len < 4: no entries.  off = 4; for i < numEntries { off+9 > len: break;
+//              keySize, valueSize, deleted = (byte == 1); off += 9; off+keySize+valueSize > len: break
+//              (64-bit sums); yield; off += keySize + valueSize }
+//   merge:     Less is by key alone (every Sequence is 0, :119), so one entry per distinct key comes out in
+//              ascending key order; which of several equal-key entries it is depends on container/heap's
+//              array order.  Here it is the entry of the lowest-numbered run (the one departure, see
+//              seb_bloom.h).  targetLevel == 4 drops a surviving tombstone (:276).
+// One walk serves plan and emit: out == nullptr only sizes.
+
+uint32_t block_entries(const uint8_t *block, uint64_t len, uint16_t *entry_off, uint32_t cap) {
+    if (len < 4) return 0;
+    const uint32_t num = le32(block);
+    uint64_t off = 4;
+    uint32_t c = 0;
+    for (uint32_t i = 0; i < num; ++i) {
+        if (off + 9 > len) break;
+        const uint64_t ks = le32(block + off), vs = le32(block + off + 4);
+        if (off + 9 + ks + vs > len) break;
+        if (c < cap) entry_off[c] = (uint16_t)off;
+        ++c;
+        off += 9 + ks + vs;
+    }
+    return c;
+}
+
+namespace {
+struct MergeEnt {
+    const uint8_t *p;  // the entry's 9-byte header; the key follows it, the value follows the key
+    uint32_t ks, vs;
+};
+inline int ent_cmp(const MergeEnt &a, const MergeEnt &b) {
+    const uint32_t n = a.ks < b.ks ? a.ks : b.ks;
+    const int c = n ? memcmp(a.p + 9, b.p + 9, n) : 0;
+    return c ? c : a.ks < b.ks ? -1 : a.ks > b.ks ? 1 : 0;
+}
+}  // namespace
+
+// 0; -1 a null argument or a run_begin that decreases; -2 a run that is not strictly increasing (*err_run,
+// *err_entry: the lowest-numbered such run and its first entry that is not above its predecessor); -3 out of
+// memory; -4 2^32 entries or more; -5 (out != nullptr) the walk does not fit `want`.
+int merge_walk(const uint8_t *pool, const uint16_t *blen, const uint64_t *run_begin, uint32_t num_runs, uint32_t flags,
+               const MergeOut *out, const MergeSizes *want, MergeSizes *sz, uint32_t *err_run, uint64_t *err_entry) {
+    if (!sz || (num_runs && !run_begin)) return -1;
+    *sz = MergeSizes{0, 0, 0, 0, 0, 0};
+    for (uint32_t r = 0; r < num_runs; ++r)
+        if (run_begin[r + 1] < run_begin[r]) return -1;
+    const uint64_t nblocks = num_runs ? run_begin[num_runs] : 0;
+    if (num_runs && nblocks > run_begin[0] && (!pool || !blen)) return -1;  // num_runs == 0: run_begin may be null
+    if (out && (!out->key_off || !out->val_off || !want)) return -1;
+    try {
+        std::vector<MergeEnt> ents;
+        std::vector<uint64_t> first(num_runs + 1, 0);
+        uint16_t offs[kMaxBlockEntries];
+        for (uint32_t r = 0; r < num_runs; ++r) {
+            first[r] = ents.size();
+            for (uint64_t b = run_begin[r]; b < run_begin[r + 1]; ++b) {
+                const uint8_t *blk = pool + b * kBlockBytes;
+                const uint64_t len = blen[b] < kBlockBytes ? blen[b] : kBlockBytes;
+                const uint32_t c = block_entries(blk, len, offs, kMaxBlockEntries);
+                for (uint32_t i = 0; i < c; ++i) ents.push_back(MergeEnt{blk + offs[i], le32(blk + offs[i]), le32(blk + offs[i] + 4)});
+            }
+            if (ents.size() >= (1ull << 32)) return -4;
+        }
+        first[num_runs] = ents.size();
+        MergeSizes s{ents.size(), 0, 0, 0, 0, 0};
+        for (uint32_t r = 0; r < num_runs; ++r)
+            for (uint64_t e = first[r] + 1; e < first[r + 1]; ++e)
+                if (ent_cmp(ents[e - 1], ents[e]) >= 0) {
+                    if (err_run) *err_run = r;
+                    if (err_entry) *err_entry = e - first[r];
+                    *sz = s;
+                    return -2;
+                }
+        // a binary heap of run cursors, least key first, the lower-numbered run first among equal keys: the
+        // first entry popped of each key is the survivor
+        std::vector<uint64_t> cur(first.begin(), first.end() - 1);
+        auto after = [&](uint32_t a, uint32_t b) {  // a comes out after b
+            const int c = ent_cmp(ents[cur[a]], ents[cur[b]]);
+            return c ? c > 0 : a > b;
+        };
+        std::vector<uint32_t> heap;
+        for (uint32_t r = 0; r < num_runs; ++r)
+            if (cur[r] < first[r + 1]) heap.push_back(r);
+        std::make_heap(heap.begin(), heap.end(), after);
+        const MergeEnt *last = nullptr;
+        if (out) out->key_off[0] = out->val_off[0] = 0;
+        while (!heap.empty()) {
+            std::pop_heap(heap.begin(), heap.end(), after);
+            const uint32_t r = heap.back();
+            const MergeEnt &e = ents[cur[r]];
+            if (++cur[r] < first[r + 1])
+                std::push_heap(heap.begin(), heap.end(), after);
+            else
+                heap.pop_back();
+            if (last && ent_cmp(*last, e) == 0) {
+                ++s.shadowed;
+                continue;
+            }
+            last = &e;
+            const bool del = e.p[8] == 1;
+            if (del && (flags & 1u)) {
+                ++s.dropped;
+                continue;
+            }
+            if (out) {
+                if (s.entries_out >= want->entries_out || s.key_bytes + e.ks > want->key_bytes ||
+                    s.val_bytes + e.vs > want->val_bytes || (e.ks && !out->keys) || (e.vs && !out->vals) || !out->deleted)
+                    return -5;
+                if (e.ks) memcpy(out->keys + s.key_bytes, e.p + 9, e.ks);
+                if (e.vs) memcpy(out->vals + s.val_bytes, e.p + 9 + e.ks, e.vs);
+                out->deleted[s.entries_out] = del ? 1 : 0;
+                out->key_off[s.entries_out + 1] = s.key_bytes + e.ks;
+                out->val_off[s.entries_out + 1] = s.val_bytes + e.vs;
+            }
+            ++s.entries_out;
+            s.key_bytes += e.ks;
+            s.val_bytes += e.vs;
+        }
+        *sz = s;
+        return 0;
+    } catch (const std::bad_alloc &) {
+        return -3;
+    }
 }
 
 }  // namespace seb

@@ -1,5 +1,5 @@
 // seb_block.h — the host-only code of seb_block.cpp (no HIP dependency): the block walker, the
-// read-list builder and the host half of the SSTable builder.
+// read-list builder, the host half of the SSTable builder and the host half of the compaction merge.
 #pragma once
 #include <cstdint>
 
@@ -32,5 +32,27 @@ int sst_walk(const SstKeys &k, const uint8_t *vals, const uint64_t *voff, const 
              SstSizes *sz);
 // [indexOffset u64][bloomOffset u64][metadataOffset u64][0x5354424C u32]
 void sst_footer(uint64_t index_offset, uint64_t bloom_offset, uint64_t metadata_offset, uint8_t *out28);
+
+// The host half of the compaction merge.
+constexpr uint32_t kMaxBlockEntries = 454;  // 4 + 9 * 455 > 4096
+// loadBlock's walk: the number of entries of block[0, len), len <= 4096; the first min(count, cap) headers'
+// offsets go to entry_off.
+uint32_t block_entries(const uint8_t *block, uint64_t len, uint16_t *entry_off, uint32_t cap);
+struct MergeSizes {  // seb_merge_sizes
+    uint64_t entries_in, entries_out, key_bytes, val_bytes, shadowed, dropped;
+};
+struct MergeOut {  // the run in the builder's layout: entries_out + 1 offsets each
+    uint8_t *keys;
+    uint64_t *key_off;
+    uint8_t *vals;
+    uint64_t *val_off;
+    uint8_t *deleted;
+};
+// mergeFiles' loop over the runs of a block pool: out == nullptr sizes only; with out, nothing past `want`
+// (a plan's sizes) is written.  0; -1 a null argument or a run_begin that decreases; -2 a run that is not
+// strictly increasing (*err_run, *err_entry); -3 out of memory; -4 2^32 entries or more; -5 the walk does not
+// fit `want`.
+int merge_walk(const uint8_t *pool, const uint16_t *blen, const uint64_t *run_begin, uint32_t num_runs, uint32_t flags,
+               const MergeOut *out, const MergeSizes *want, MergeSizes *sz, uint32_t *err_run, uint64_t *err_entry);
 
 }  // namespace seb

@@ -5,7 +5,7 @@
 //   seb_ctx.cpp       contexts, the chunk loops, seb_build / seb_probe / seb_probe_multi
 //   seb_filter.cpp    the Go-API filter handle and its CPU fallback
 //   seb_registry.cpp  the registry, MultiGet, the index walk and the block locator
-//   seb_sstable.cpp   the block-search and SSTable-builder entry points
+//   seb_sstable.cpp   the block-search, SSTable-builder and compaction-merge entry points
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -215,6 +215,7 @@ struct seb_ctx {
     seb::DevBuf keys[2], offs[2], out[2], words, filt, ws;
     seb::DevBuf sb_bid, sb_pool, sb_blen, sb_cells, sb_out;  // seb_search_blocks: its inputs and outputs on the device
     seb::DevBuf sst_in, sst_ws, sst_out;  // seb_sst_build: the run, the plan's workspace, the three sections
+    seb::DevBuf mrg_in, mrg_ws, mrg_out;  // seb_merge: pool + blen + counts, the plan's workspace, the five output arrays
     seb::PinBuf hkeys, hbits;  // small filter builds: keys in, bits out, read and written by the kernels
     uint64_t chunk_bytes = 64ull << 20;
     std::vector<uint64_t> off_tmp[2];

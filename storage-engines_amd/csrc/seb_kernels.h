@@ -184,6 +184,41 @@ hipError_t launch_sst_encode(const KeyBatch &kb, const uint8_t *vals, const uint
                              uint64_t meta_total, uint8_t *data, uint16_t *blen, uint8_t *index, uint8_t *meta,
                              hipStream_t s);
 
+// seb_merge.hip: the batched compaction merge (lsm/compaction.go:69-124,226-333): k sorted runs of a block
+// pool into one sorted, de-duplicated run in the builder's input layout.  The plan lives in a caller-provided
+// workspace: a 128-byte header, then arrays at these offsets, all 16-byte aligned.
+constexpr uint32_t kMergeTile = 1024;  // records per tile of a merge pass, of the survivor scan and of the emit
+constexpr uint32_t kMergeMaxRuns = 1u << 20;  // SEB_MERGE_MAX_RUNS
+struct MergeWs {
+    uint64_t bytes, head_bytes, tiles;
+    // per run, per block, per 256 blocks: placed before anything that depends on n
+    uint64_t run_begin, run_first, block_first, groups;
+    // per tile x 3, per entry x 2, the passes' tile tables, one pass's cuts
+    uint64_t sums, rec_a, rec_b, tab, tab_cap, cuts;
+    uint32_t passes;
+};
+MergeWs merge_ws_layout(uint64_t n, uint32_t num_blocks, uint32_t num_runs);
+uint64_t merge_emit_min_bytes(uint64_t n);  // the least workspace a plan of n entries can have
+hipError_t launch_merge_count(const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, uint16_t *block_entries,
+                              hipStream_t s);
+// The plan in three steps, each of which synchronises the stream (num_runs >= 1, num_blocks >= 1):
+// head: the blocks' first records; *n_host = the entry count, run_first_host[num_runs + 1] = the runs' first
+// records (needs head_bytes of workspace); decode (n >= 1, n < 2^32, the whole workspace): the records and the
+// order check, *err_host = run << 32 | entry of the least offender, all ones for none; tree: the merge
+// passes and the survivors, sizes_host = one seb_merge_sizes.
+hipError_t launch_merge_head(const uint64_t *run_begin_host, uint32_t num_runs, const uint16_t *block_entries,
+                             uint32_t num_blocks, void *ws, uint64_t *n_host, uint64_t *run_first_host, hipStream_t s);
+hipError_t launch_merge_decode(const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, uint32_t num_runs,
+                               uint64_t n, void *ws, uint64_t *err_host, hipStream_t s);
+hipError_t launch_merge_tree(const uint8_t *pool, uint32_t num_blocks, uint32_t num_runs, uint64_t n,
+                             const uint64_t *run_first_host, uint32_t flags, void *ws, void *sizes_host, hipStream_t s);
+// *ok = the workspace's header is the plan's that returned `sizes` (one seb_merge_sizes) and its arrays lie inside
+// ws_bytes; reads the header back, so it waits for what the stream holds.
+hipError_t merge_ws_check(const void *sizes, const void *ws, uint64_t ws_bytes, bool *ok, hipStream_t s);
+// sizes: one seb_merge_sizes with entries_in >= 1; nothing past its entries_out / key_bytes / val_bytes is written.
+hipError_t launch_merge_emit(const uint8_t *pool, const void *sizes, const void *ws, uint8_t *keys, uint64_t *key_off,
+                             uint8_t *vals, uint64_t *val_off, uint8_t *deleted, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

@@ -1,6 +1,8 @@
-// seb_sstable.cpp — the entry points of the batched data-block search and of the batched SSTable
-// builder: the C ABI over their host halves (seb_block.cpp) and their kernels (seb_search.hip,
-// seb_sst.hip), and the host-buffer forms through a context.
+// seb_sstable.cpp — the entry points of the batched data-block search, of the batched SSTable
+// builder and of the batched compaction merge: the C ABI over their host halves (seb_block.cpp) and
+// their kernels (seb_search.hip, seb_sst.hip, seb_merge.hip), and the host-buffer forms through a context.
+#include <new>
+
 #include "seb_block.h"
 #include "seb_host.h"
 
@@ -316,6 +318,253 @@ extern "C" int seb_sst_build(seb_ctx *c, const seb_keys *kb, const uint8_t *vals
     HIP_OR_FAIL(hipMemcpyAsync(out, dout, sz.data_bytes, hipMemcpyDeviceToHost, s));
     HIP_OR_FAIL(hipMemcpyAsync(out + o_index, dout + a_index, sz.index_bytes, hipMemcpyDeviceToHost, s));
     HIP_OR_FAIL(hipMemcpyAsync(out + o_meta, dout + a_metao, sz.meta_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipStreamSynchronize(s));
+    return SEB_OK;
+}
+
+// ------------------------------------------------ batched compaction merge (lsm/compaction.go:69-124,226-333)
+
+static_assert(sizeof(seb_merge_sizes) == sizeof(seb::MergeSizes) && sizeof(seb_merge_sizes) == 48, "seb_merge_sizes layout");
+
+extern "C" int seb_block_entries(const uint8_t *block, uint64_t len, uint16_t *entry_off, uint32_t cap, uint32_t *count) {
+    const char *who = "seb_block_entries";
+    if (len > SEB_BLOCK_BYTES)
+        return fail(SEB_ERR_INVALID, "%s: %llu bytes > the 4096 readBlock returns", who, (unsigned long long)len);
+    if (!count || (len && !block) || (cap && !entry_off)) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    *count = seb::block_entries(block, len, entry_off, cap);
+    if (*count > cap)
+        return fail(SEB_ERR_RANGE, "%s: %u entries > cap %u; retry with *count", who, *count, cap);
+    return SEB_OK;
+}
+
+static int merge_host_rc(int rc, uint32_t run, uint64_t entry, const char *who) {
+    switch (rc) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_INVALID, "%s: run %u entry %llu is not above its predecessor (every run must be strictly "
+                    "increasing)", who, run, (unsigned long long)entry);
+    case -3:
+        return fail(SEB_ERR_NOMEM, "%s: out of host memory", who);
+    case -4:
+        return fail(SEB_ERR_INVALID, "%s: 2^32 entries or more", who);
+    case -5:
+        return fail(SEB_ERR_INVALID, "%s: sizes are not this input's plan", who);
+    default:
+        return fail(SEB_ERR_INVALID, "%s: null argument, or run_begin decreases", who);
+    }
+}
+
+static int check_merge_runs(const uint64_t *run_begin, uint32_t num_runs, const char *who) {
+    if (num_runs > SEB_MERGE_MAX_RUNS)
+        return fail(SEB_ERR_INVALID, "%s: %u runs > SEB_MERGE_MAX_RUNS", who, num_runs);
+    if (num_runs && !run_begin) return fail(SEB_ERR_INVALID, "%s: null run_begin", who);
+    return SEB_OK;
+}
+
+extern "C" int seb_merge_plan(const uint8_t *pool, const uint16_t *blen, const uint64_t *run_begin, uint32_t num_runs,
+                              uint32_t flags, seb_merge_sizes *sizes) {
+    const char *who = "seb_merge_plan";
+    int rc;
+    if ((rc = check_merge_runs(run_begin, num_runs, who))) return rc;
+    uint32_t run = 0;
+    uint64_t entry = 0;
+    rc = seb::merge_walk(pool, blen, run_begin, num_runs, flags, nullptr, nullptr, (seb::MergeSizes *)sizes, &run, &entry);
+    return merge_host_rc(rc, run, entry, who);
+}
+
+extern "C" int seb_merge_emit(const uint8_t *pool, const uint16_t *blen, const uint64_t *run_begin, uint32_t num_runs,
+                              uint32_t flags, uint8_t *keys, uint64_t *key_off, uint8_t *vals, uint64_t *val_off,
+                              uint8_t *deleted, const seb_merge_sizes *sizes) {
+    const char *who = "seb_merge_emit";
+    int rc;
+    if ((rc = check_merge_runs(run_begin, num_runs, who))) return rc;
+    if (!sizes) return fail(SEB_ERR_INVALID, "%s: null sizes", who);
+    uint32_t run = 0;
+    uint64_t entry = 0;
+    const seb::MergeOut out{keys, key_off, vals, val_off, deleted};
+    seb::MergeSizes got;
+    rc = seb::merge_walk(pool, blen, run_begin, num_runs, flags, &out, (const seb::MergeSizes *)sizes, &got, &run, &entry);
+    if (rc == 0 && memcmp(&got, sizes, sizeof got) != 0) rc = -5;
+    return merge_host_rc(rc, run, entry, who);
+}
+
+static int check_merge_dev_args(const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks, const uint64_t *run_begin,
+                                uint32_t num_runs, const void *block_entries, const char *who, bool aligned = true) {
+    int rc;
+    if ((rc = check_merge_runs(run_begin, num_runs, who))) return rc;
+    if (num_runs == 0) {
+        if (num_blocks) return fail(SEB_ERR_INVALID, "%s: %u blocks in no run", who, num_blocks);
+        return SEB_OK;
+    }
+    if (run_begin[0] != 0 || run_begin[num_runs] != num_blocks)
+        return fail(SEB_ERR_INVALID, "%s: run_begin must run from 0 to num_blocks = %u", who, num_blocks);
+    for (uint32_t r = 0; r < num_runs; ++r)
+        if (run_begin[r + 1] < run_begin[r]) return fail(SEB_ERR_INVALID, "%s: run_begin decreases at %u", who, r);
+    if (num_blocks && (!pool || !blen || !block_entries)) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if (aligned && ((uintptr_t)pool & 15)) return fail(SEB_ERR_INVALID, "%s: the block pool is not 16-byte aligned", who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_merge_count(const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks,
+                                   const uint64_t *run_begin, uint32_t num_runs, uint16_t *block_entries,
+                                   uint64_t *run_entries, void *stream) {
+    const char *who = "seb_dev_merge_count";
+    enter();
+    int rc;
+    if ((rc = check_merge_dev_args(pool, blen, num_blocks, run_begin, num_runs, block_entries, who))) return rc;
+    if (run_entries)
+        for (uint32_t r = 0; r < num_runs; ++r) run_entries[r] = 0;
+    if (num_blocks == 0) return SEB_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OR_FAIL(launch_merge_count(pool, blen, num_blocks, block_entries, s));
+    std::vector<uint16_t> cnt;
+    try {
+        cnt.resize(run_entries ? num_blocks : 0);
+    } catch (const std::bad_alloc &) {
+        return fail(SEB_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    if (run_entries) HIP_OR_FAIL(hipMemcpyAsync(cnt.data(), block_entries, 2ull * num_blocks, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipStreamSynchronize(s));
+    if (run_entries)
+        for (uint32_t r = 0; r < num_runs; ++r)
+            for (uint64_t b = run_begin[r]; b < run_begin[r + 1]; ++b) run_entries[r] += cnt[b];
+    return SEB_OK;
+}
+
+extern "C" uint64_t seb_dev_merge_workspace_size(uint64_t entries, uint32_t num_blocks, uint32_t num_runs) {
+    if (entries >= (1ull << 32) || num_runs > SEB_MERGE_MAX_RUNS) return 0;
+    return merge_ws_layout(entries, num_blocks, num_runs).bytes;
+}
+
+extern "C" int seb_dev_merge_plan(const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks,
+                                  const uint64_t *run_begin, uint32_t num_runs, const uint16_t *block_entries,
+                                  uint32_t flags, void *ws, uint64_t ws_bytes, seb_merge_sizes *sizes, void *stream) {
+    const char *who = "seb_dev_merge_plan";
+    enter();
+    int rc;
+    if ((rc = check_merge_dev_args(pool, blen, num_blocks, run_begin, num_runs, block_entries, who))) return rc;
+    if (!sizes) return fail(SEB_ERR_INVALID, "%s: null sizes", who);
+    *sizes = seb_merge_sizes{0, 0, 0, 0, 0, 0};
+    if (num_blocks == 0) return SEB_OK;
+    if (!ws || ((uintptr_t)ws & 15)) return fail(SEB_ERR_INVALID, "%s: the workspace is null or not 16-byte aligned", who);
+    const uint64_t head = merge_ws_layout(0, num_blocks, num_runs).head_bytes;
+    if (ws_bytes < head)
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes", who, (unsigned long long)ws_bytes,
+                    (unsigned long long)head);
+    hipStream_t s = (hipStream_t)stream;
+    try {
+        std::vector<uint64_t> run_first((size_t)num_runs + 1);
+        uint64_t n = 0;
+        HIP_OR_FAIL(launch_merge_head(run_begin, num_runs, block_entries, num_blocks, ws, &n, run_first.data(), s));
+        if (n >= (1ull << 32)) return fail(SEB_ERR_INVALID, "%s: 2^32 entries or more", who);
+        sizes->entries_in = n;
+        if (n == 0) return SEB_OK;
+        const uint64_t want = merge_ws_layout(n, num_blocks, num_runs).bytes;
+        if (ws_bytes < want)
+            return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes for %llu entries", who,
+                        (unsigned long long)ws_bytes, (unsigned long long)want, (unsigned long long)n);
+        uint64_t err = 0;
+        HIP_OR_FAIL(launch_merge_decode(pool, blen, num_blocks, num_runs, n, ws, &err, s));
+        if (err != UINT64_MAX)
+            return merge_host_rc(-2, (uint32_t)(err >> 32), err & 0xFFFFFFFFull, who);
+        HIP_OR_FAIL(launch_merge_tree(pool, num_blocks, num_runs, n, run_first.data(), flags, ws, sizes, s));
+    } catch (const std::bad_alloc &) {
+        return fail(SEB_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_merge_emit(const uint8_t *pool, const seb_merge_sizes *sizes, const void *ws, uint64_t ws_bytes,
+                                  uint8_t *keys, uint64_t *key_off, uint8_t *vals, uint64_t *val_off, uint8_t *deleted,
+                                  void *stream) {
+    const char *who = "seb_dev_merge_emit";
+    enter();
+    if (!sizes || !key_off || !val_off) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if (sizes->entries_out > sizes->entries_in || sizes->entries_in >= (1ull << 32) ||
+        sizes->entries_in - sizes->entries_out != sizes->shadowed + sizes->dropped ||
+        sizes->key_bytes > 4096 * sizes->entries_out || sizes->val_bytes > 4096 * sizes->entries_out)
+        return fail(SEB_ERR_INVALID, "%s: sizes are not a plan's", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (sizes->entries_in == 0) {  // nothing to launch: the two first offsets alone
+        HIP_OR_FAIL(hipMemsetAsync(key_off, 0, 8, s));
+        HIP_OR_FAIL(hipMemsetAsync(val_off, 0, 8, s));
+        return SEB_OK;
+    }
+    if (!pool || !ws || ((uintptr_t)ws & 15) || ((uintptr_t)pool & 15))
+        return fail(SEB_ERR_INVALID, "%s: the pool or the workspace is null or not 16-byte aligned", who);
+    if (ws_bytes < merge_emit_min_bytes(sizes->entries_in))
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu bytes is not a plan's of %llu entries", who,
+                    (unsigned long long)ws_bytes, (unsigned long long)sizes->entries_in);
+    if ((sizes->entries_out && !deleted) || (sizes->key_bytes && !keys) || (sizes->val_bytes && !vals))
+        return fail(SEB_ERR_INVALID, "%s: null output", who);
+    bool ok = false;  // the plan synchronised, so reading the header back waits only for what the caller enqueued since
+    HIP_OR_FAIL(merge_ws_check(sizes, ws, ws_bytes, &ok, s));
+    if (!ok) return fail(SEB_ERR_INVALID, "%s: the workspace does not hold the plan that returned these sizes", who);
+    HIP_OR_FAIL(launch_merge_emit(pool, sizes, ws, keys, key_off, vals, val_off, deleted, s));
+    return SEB_OK;
+}
+
+// Host buffers through the context: the pool and blen go up in one piece, count, plan and emit run on the
+// compute stream, and the five arrays come back.
+extern "C" int seb_merge(seb_ctx *c, const uint8_t *pool, const uint16_t *blen, uint32_t num_blocks,
+                         const uint64_t *run_begin, uint32_t num_runs, uint32_t flags, uint8_t *keys, uint64_t key_cap,
+                         uint64_t *key_off, uint8_t *vals, uint64_t val_cap, uint64_t *val_off, uint8_t *deleted,
+                         uint64_t entry_cap, seb_merge_sizes *sizes) {
+    const char *who = "seb_merge";
+    int rc;
+    if (!c) return fail(SEB_ERR_INVALID, "%s: null ctx", who);
+    if (!sizes || !key_off || !val_off) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    if ((rc = check_merge_dev_args(pool, blen, num_blocks, run_begin, num_runs, blen, who, false))) return rc;
+    *sizes = seb_merge_sizes{0, 0, 0, 0, 0, 0};
+    key_off[0] = val_off[0] = 0;
+    if (num_blocks == 0) return SEB_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OR_FAIL(hipSetDevice(c->device));
+    hipStream_t s = c->s_comp;
+    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t pool_bytes = (uint64_t)num_blocks * SEB_BLOCK_BYTES, a_blen = pool_bytes, a_cnt = a_blen + up(2ull * num_blocks);
+    if ((rc = c->mrg_in.reserve(a_cnt + up(2ull * num_blocks)))) return rc;
+    uint8_t *in = (uint8_t *)c->mrg_in.p;
+    HIP_OR_FAIL(hipMemcpyAsync(in, pool, pool_bytes, hipMemcpyHostToDevice, s));
+    HIP_OR_FAIL(hipMemcpyAsync(in + a_blen, blen, 2ull * num_blocks, hipMemcpyHostToDevice, s));
+    std::vector<uint64_t> run_entries;
+    try {
+        run_entries.resize(num_runs);
+    } catch (const std::bad_alloc &) {
+        return fail(SEB_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    if ((rc = seb_dev_merge_count(in, (const uint16_t *)(in + a_blen), num_blocks, run_begin, num_runs,
+                                  (uint16_t *)(in + a_cnt), run_entries.data(), s)))
+        return rc;
+    uint64_t n = 0;
+    for (uint64_t e : run_entries) n += e;
+    if (n >= (1ull << 32)) return fail(SEB_ERR_INVALID, "%s: 2^32 entries or more", who);
+    const uint64_t ws_bytes = merge_ws_layout(n, num_blocks, num_runs).bytes;
+    if ((rc = c->mrg_ws.reserve(ws_bytes, true))) return rc;
+    if ((rc = seb_dev_merge_plan(in, (const uint16_t *)(in + a_blen), num_blocks, run_begin, num_runs,
+                                 (const uint16_t *)(in + a_cnt), flags, c->mrg_ws.p, ws_bytes, sizes, s)))
+        return rc;
+    if (sizes->entries_out > entry_cap || sizes->key_bytes > key_cap || sizes->val_bytes > val_cap)
+        return fail(SEB_ERR_RANGE, "%s: a capacity is below its size (%llu entries, %llu key bytes, %llu value bytes); "
+                    "retry with *sizes", who, (unsigned long long)sizes->entries_out, (unsigned long long)sizes->key_bytes,
+                    (unsigned long long)sizes->val_bytes);
+    if (sizes->entries_in == 0) return SEB_OK;
+    const uint64_t no = sizes->entries_out;
+    if ((no && !deleted) || (sizes->key_bytes && !keys) || (sizes->val_bytes && !vals))
+        return fail(SEB_ERR_INVALID, "%s: null output", who);
+    const uint64_t o_koff = up(sizes->key_bytes), o_vals = o_koff + up(8 * (no + 1)), o_voff = o_vals + up(sizes->val_bytes),
+                   o_del = o_voff + up(8 * (no + 1)), out_bytes = o_del + up(no);
+    if ((rc = c->mrg_out.reserve(std::max<uint64_t>(out_bytes, 16)))) return rc;
+    uint8_t *o = (uint8_t *)c->mrg_out.p;
+    if ((rc = seb_dev_merge_emit(in, sizes, c->mrg_ws.p, ws_bytes, o, (uint64_t *)(o + o_koff), o + o_vals,
+                                 (uint64_t *)(o + o_voff), o + o_del, s)))
+        return rc;
+    if (sizes->key_bytes) HIP_OR_FAIL(hipMemcpyAsync(keys, o, sizes->key_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipMemcpyAsync(key_off, o + o_koff, 8 * (no + 1), hipMemcpyDeviceToHost, s));
+    if (sizes->val_bytes) HIP_OR_FAIL(hipMemcpyAsync(vals, o + o_vals, sizes->val_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipMemcpyAsync(val_off, o + o_voff, 8 * (no + 1), hipMemcpyDeviceToHost, s));
+    if (no) HIP_OR_FAIL(hipMemcpyAsync(deleted, o + o_del, no, hipMemcpyDeviceToHost, s));
     HIP_OR_FAIL(hipStreamSynchronize(s));
     return SEB_OK;
 }

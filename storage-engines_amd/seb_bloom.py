@@ -52,6 +52,14 @@ class seb_sst_sizes(C.Structure):
         return (self.num_blocks, self.data_bytes, self.index_bytes, self.meta_bytes, self.oversize_entries)
 
 
+class seb_merge_sizes(C.Structure):
+    _fields_ = [("entries_in", C.c_uint64), ("entries_out", C.c_uint64), ("key_bytes", C.c_uint64),
+                ("val_bytes", C.c_uint64), ("shadowed", C.c_uint64), ("dropped", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.entries_in, self.entries_out, self.key_bytes, self.val_bytes, self.shadowed, self.dropped)
+
+
 class seb_filter_ref(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("num_bits", C.c_uint64), ("num_hashes", C.c_uint32),
                 ("reserved", C.c_uint32)]
@@ -137,6 +145,15 @@ _SIGS = {
     "seb_dev_sst_encode": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, C.POINTER(_u64), _u32, C.POINTER(seb_sst_sizes), _vp,
                                 _u64, _vp, _vp, _vp, _vp, _vp]),
     "seb_sst_build": (_i, [_vp, C.POINTER(seb_keys), _vp, _vp, _vp, C.c_int64, _vp, _u64, C.POINTER(_u64)]),
+    "seb_block_entries": (_i, [_vp, _u64, _vp, _u32, C.POINTER(_u32)]),
+    "seb_merge_plan": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(seb_merge_sizes)]),
+    "seb_merge_emit": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(seb_merge_sizes)]),
+    "seb_dev_merge_count": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "seb_dev_merge_workspace_size": (_u64, [_u64, _u32, _u32]),
+    "seb_dev_merge_plan": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u64, C.POINTER(seb_merge_sizes), _vp]),
+    "seb_dev_merge_emit": (_i, [_vp, C.POINTER(seb_merge_sizes), _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_merge": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64,
+                       C.POINTER(seb_merge_sizes)]),
     "seb_workspace_bytes": (_u64, []),
     "seb_dev_or_slices": (_i, [_vp, _u32, _u64, _vp, _vp]),
     "seb_workspace_release": (_i, []),
@@ -364,6 +381,28 @@ class Ctx:
                 continue
             check(rc)
             return out[: need.value].tobytes()
+
+    def merge(self, pool, blen, run_begin, flags: int = 0, caps: tuple[int, int, int] | None = None):
+        """The compaction merge from host memory: run r = blocks [run_begin[r], run_begin[r+1]) of the pool
+        (4096-byte slots, blen their lengths).  Returns (keys u8, key_off u64, vals u8, val_off u64,
+        deleted u8, sizes) of the merged run; caps = (key bytes, value bytes, entries) fixes the output
+        capacities instead of retrying with the sizes a too small first call reports."""
+        pool, blen, rb, nb, nr = _merge_host_args(pool, blen, run_begin)
+        kc, vc, ec = caps if caps is not None else (0, 0, 0)
+        sz = seb_merge_sizes()
+        while True:
+            out = _merge_out(kc, vc, ec)
+            rc = lib().seb_merge(self._p, pool.ctypes.data if nb else None, blen.ctypes.data if nb else None, nb,
+                                 rb.ctypes.data if nr else None, nr, flags, out[0].ctypes.data, kc, out[1].ctypes.data,
+                                 out[2].ctypes.data, vc, out[3].ctypes.data, out[4].ctypes.data, ec, C.byref(sz))
+            if rc == -4 and caps is None and (sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
+                kc, vc, ec = sz.key_bytes, sz.val_bytes, sz.entries_out
+                continue
+            if rc < 0:  # SEB_ERR_RANGE fills the sizes: the exception carries them
+                err = SebError(rc, last_error())
+                err.sizes = sz.as_tuple()
+                raise err
+            return _merge_trim(out, sz)
 
     def probe_multi(self, keys, filters: list[tuple[np.ndarray, int, int]]) -> np.ndarray:
         kb = as_keys(keys)
@@ -956,6 +995,129 @@ def sst_build(keys, vals, val_off, deleted=None, expected_keys: int | None = Non
     ctx = Ctx(device)
     try:
         return ctx.sst_build(keys, vals, val_off, deleted, expected_keys)
+    finally:
+        ctx.close()
+
+
+# ------------------------------- batched compaction merge (lsm/compaction.go:69-124,226-333)
+
+MERGE_DROP_TOMBSTONES = 1  # SEB_MERGE_DROP_TOMBSTONES: targetLevel == 4
+MERGE_MAX_RUNS = 1 << 20   # SEB_MERGE_MAX_RUNS
+MERGE_TILE = 1024          # kMergeTile: records per tile of a merge pass, of the survivor scan and of the emit
+MAX_BLOCK_ENTRIES = 454    # the most entries a 4096-byte block yields
+
+
+def block_entries(block: bytes, cap: int = MAX_BLOCK_ENTRIES) -> np.ndarray:
+    """loadBlock's walk on the host for one block image (at most 4096 bytes): the offsets (u16) of the
+    entries' 9-byte headers.  More than cap entries: SebError (RANGE) whose .count is the number found."""
+    off = np.zeros(max(cap, 1), np.uint16)
+    count = _u32(0)
+    rc = lib().seb_block_entries(bytes(block), len(block), off.ctypes.data, cap, C.byref(count))
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.count = count.value
+        raise err
+    return off[: count.value].copy()
+
+
+def _merge_host_args(pool, blen, run_begin):
+    pool = np.ascontiguousarray(pool, dtype=np.uint8).reshape(-1)
+    blen = np.ascontiguousarray(blen, dtype=np.uint16)
+    rb = np.ascontiguousarray(run_begin, dtype=np.uint64)
+    nb, nr = blen.size, max(rb.size - 1, 0)
+    if pool.size < nb * BLOCK_BYTES:
+        raise ValueError(f"pool holds {pool.size} bytes, {nb} blocks need {nb * BLOCK_BYTES}")
+    if nr and int(rb[-1]) > nb:
+        raise ValueError(f"run_begin ends at {int(rb[-1])}, blen holds {nb} blocks")
+    return pool, blen, rb, nb, nr
+
+
+def _merge_out(key_bytes: int, val_bytes: int, entries: int):
+    return (np.zeros(max(key_bytes, 1), np.uint8), np.zeros(entries + 1, np.uint64), np.zeros(max(val_bytes, 1), np.uint8),
+            np.zeros(entries + 1, np.uint64), np.zeros(max(entries, 1), np.uint8))
+
+
+def _merge_trim(out, sz):
+    n = sz.entries_out
+    return out[0][: sz.key_bytes], out[1][: n + 1], out[2][: sz.val_bytes], out[3][: n + 1], out[4][:n], sz.as_tuple()
+
+
+def merge_plan(pool, blen, run_begin, flags: int = 0) -> tuple[int, int, int, int, int, int]:
+    """The host half's plan: (entries_in, entries_out, key_bytes, val_bytes, shadowed, dropped) of the merge
+    of the pool's runs.  A run that is not strictly increasing: SebError (INVALID) naming run and entry."""
+    pool, blen, rb, nb, nr = _merge_host_args(pool, blen, run_begin)
+    sz = seb_merge_sizes()
+    check(lib().seb_merge_plan(pool.ctypes.data if nb else None, blen.ctypes.data if nb else None,
+                               rb.ctypes.data if nr else None, nr, flags, C.byref(sz)))
+    return sz.as_tuple()
+
+
+def merge_emit(pool, blen, run_begin, flags: int = 0, sizes=None):
+    """The host half: (keys u8, key_off u64, vals u8, val_off u64, deleted u8, sizes) of the merged run;
+    sizes default to merge_plan's."""
+    pool, blen, rb, nb, nr = _merge_host_args(pool, blen, run_begin)
+    sz = seb_merge_sizes(*(merge_plan(pool, blen, rb, flags) if sizes is None else sizes))
+    out = _merge_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
+    check(lib().seb_merge_emit(pool.ctypes.data if nb else None, blen.ctypes.data if nb else None,
+                               rb.ctypes.data if nr else None, nr, flags, out[0].ctypes.data, out[1].ctypes.data,
+                               out[2].ctypes.data, out[3].ctypes.data, out[4].ctypes.data, C.byref(sz)))
+    return _merge_trim(out, sz)
+
+
+def _run_begin(run_begin):
+    rb = [int(x) for x in run_begin]
+    return rb, max(len(rb) - 1, 0), (_u64 * max(len(rb), 1))(*rb)
+
+
+def dev_merge_count(pool, blen, run_begin, block_entries, stream=None) -> list[int]:
+    """Device form: block_entries (u16 tensor, one per block) = each block's entry count; synchronises and
+    returns each run's entry count."""
+    rb, nr, crb = _run_begin(run_begin)
+    nb = rb[-1] if rb else 0
+    for name, t, size in (("pool", pool, BLOCK_BYTES * nb), ("blen", blen, 2 * nb), ("block_entries", block_entries, 2 * nb)):
+        if nb and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {nb} blocks need {size}")
+    runs = (_u64 * max(nr, 1))()
+    check(lib().seb_dev_merge_count(_ptr(pool) if nb else None, _ptr(blen) if nb else None, nb, crb if nr else None, nr,
+                                    _ptr(block_entries) if nb else None, runs, _stream(stream)))
+    return [runs[r] for r in range(nr)]
+
+
+def dev_merge_workspace_size(entries: int, num_blocks: int, num_runs: int) -> int:
+    return lib().seb_dev_merge_workspace_size(entries, num_blocks, num_runs)
+
+
+def dev_merge_plan(pool, blen, run_begin, block_entries, ws, flags: int = 0, ws_bytes: int | None = None,
+                   stream=None) -> tuple[int, int, int, int, int, int]:
+    """Device form: decode, order check, merge and survivor scan into the workspace tensor `ws`
+    (dev_merge_workspace_size bytes); synchronises and returns the sizes."""
+    rb, nr, crb = _run_begin(run_begin)
+    nb = rb[-1] if rb else 0
+    sz = seb_merge_sizes()
+    check(lib().seb_dev_merge_plan(_ptr(pool) if nb else None, _ptr(blen) if nb else None, nb, crb if nr else None, nr,
+                                   _ptr(block_entries) if nb else None, flags, _ptr(ws),
+                                   (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes, C.byref(sz),
+                                   _stream(stream)))
+    return sz.as_tuple()
+
+
+def dev_merge_emit(pool, sizes, ws, keys, key_off, vals, val_off, deleted, stream=None) -> None:
+    """Device form: writes the merged run (sizes as dev_merge_plan returned them): keys / vals (u8), key_off /
+    val_off (entries_out + 1 u64 each), deleted (entries_out u8).  Not synchronised."""
+    sz = seb_merge_sizes(*sizes)
+    for name, t, size in (("keys", keys, sz.key_bytes), ("vals", vals, sz.val_bytes), ("deleted", deleted, sz.entries_out),
+                          ("key_off", key_off, 8 * (sz.entries_out + 1)), ("val_off", val_off, 8 * (sz.entries_out + 1))):
+        if (t is None and size) or (t is not None and _nbytes(t) < size):
+            raise ValueError(f"{name} holds {0 if t is None else _nbytes(t)} bytes, the plan needs {size}")
+    check(lib().seb_dev_merge_emit(_ptr(pool), C.byref(sz), _ptr(ws), _nbytes(ws) if ws is not None else 0, _ptr(keys),
+                                   _ptr(key_off), _ptr(vals), _ptr(val_off), _ptr(deleted), _stream(stream)))
+
+
+def merge(pool, blen, run_begin, flags: int = 0, caps=None, device: int = 0):
+    """Ctx.merge on a context made for the call."""
+    ctx = Ctx(device)
+    try:
+        return ctx.merge(pool, blen, run_begin, flags, caps)
     finally:
         ctx.close()
 
