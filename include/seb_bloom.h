@@ -582,6 +582,82 @@ int seb_merge(seb_ctx *ctx, const uint8_t *pool, const uint16_t *blen, uint32_t 
               uint32_t num_runs, uint32_t flags, uint8_t *keys, uint64_t key_cap, uint64_t *key_off, uint8_t *vals,
               uint64_t val_cap, uint64_t *val_off, uint8_t *deleted, uint64_t entry_cap, seb_merge_sizes *sizes);
 
+/* ------------- WAL replay: a log image into the memtable's sorted run for the builder ---- */
+/* What recoverFromWAL leaves in the memtable (lsm/lsm.go:273-298) and what flushMemtable then hands to the
+ * builder, GetAllEntries() (lsm/memtable.go:129-137, lsm/lsm.go:343-370), for a whole log image at once.
+ * Input: a WAL image and its record boundaries as seb_wal_scan yields them: record i = data[rec_off[i],
+ * rec_off[i+1]) = [crc u32][seq u64][keySize u32][valueSize u32][deleted u8][key][value], little-endian
+ * (lsm/wal.go:31-62); the image may sit at any byte alignment.
+ *
+ * Every record goes through MemTable.Put or MemTable.Delete (lsm/memtable.go:34-93) in log order:
+ *   - deleted = (byte == 1) (wal.go:114): a byte of 2 or 255 is a Put.
+ *   - a Put makes the entry (key, value, seq, not deleted); a deleted record makes (key, NO VALUE, seq,
+ *     deleted): Delete stores Value nil, so a deleted record's valueSize bytes do not come out.
+ *   - a record of a key that is there replaces the whole entry (memtable.go:51-54, 82-85).  One entry per
+ *     distinct key survives: that of the key's LAST RECORD IN LOG ORDER, even where an earlier record has the
+ *     higher seq.  Tombstones stay, as entries with deleted = 1.
+ *   - entries come out in ascending Go string order (bytewise, a key before its extensions); the empty key is
+ *     a key like any other.
+ *   - max_sequence = the maximum seq over ALL records, overwritten ones included (lsm.go:286-288); 0 for none.
+ *   - memtable_size = MemTable.size after the replay = the sum over the survivors of keyLen + 16 + valueLen
+ *     (valueLen 0 for a tombstone): Put and Delete keep it path independent (memtable.go:54,60,85,91).
+ *   - recovery never flushes: a whole log is one run.
+ * There is no departure from the reference: (key, record index) is a total order, so every output byte is
+ * determined.
+ *
+ * Output: the builder's input layout exactly as seb_dev_merge_emit writes it (keys / key_off, vals / val_off,
+ * entries_out + 1 offsets each starting at 0, deleted = 1 or 0) plus seq (nullable): seq[o] = the surviving
+ * record's sequence, which MemTable.Get returns.  Nothing outside the sizes the plan returned is written.
+ *
+ * Safety: before anything else of a record is read its framing is checked (length >= 21 and 21 + keySize +
+ * valueSize == length, 64-bit sums), and before that its offsets (rec_off[0] <= rec_off[i] <= rec_off[i+1] <=
+ * rec_off[n]).  The first record that fails either check: SEB_ERR_INVALID, and seb_last_error names it
+ * ("record R").  No byte outside [rec_off[0], rec_off[n]) is read on any input.  The CRC is NOT rechecked:
+ * that is SEB_WAL_VERIFY's job, which the caller runs first (seb_wal_recover does).  Limits: n < 2^32; key and
+ * value sizes take the full u32.  n == 0 is valid and gives an empty run. */
+typedef struct seb_replay_sizes {
+    uint64_t records_in, entries_out; /* records / surviving entries */
+    uint64_t key_bytes, val_bytes;    /* of the survivors */
+    uint64_t overwritten, tombstones; /* records lost to a later record of their key / surviving tombstones */
+    uint64_t max_sequence;            /* lsm.sequence after the recovery */
+    uint64_t memtable_size;           /* MemTable.size after the recovery */
+} seb_replay_sizes;
+
+/* Host only.  seb_wal_replay_plan sizes the output; seb_wal_replay_emit (`sizes` as the plan returned them;
+ * anything else: SEB_ERR_INVALID) writes it.  They are the reference for the device form and what a caller
+ * without a GPU uses. */
+int seb_wal_replay_plan(const uint8_t *data, const uint64_t *rec_off, uint64_t n, seb_replay_sizes *sizes);
+int seb_wal_replay_emit(const uint8_t *data, const uint64_t *rec_off, uint64_t n, uint8_t *keys, uint64_t *key_off,
+                        uint8_t *vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq,
+                        const seb_replay_sizes *sizes);
+
+/* Device pointers, rec_off included (n + 1 u64, 8-byte aligned); sizes is HOST memory.
+ * seb_dev_wal_replay_plan (workspace: seb_dev_wal_replay_workspace_size(n) bytes of device memory, 16-byte
+ * aligned, opaque; too small: SEB_ERR_INVALID) checks and decodes the records, sorts them, marks the survivors,
+ * SYNCHRONISES and fills *sizes, so the caller can allocate the outputs.
+ * seb_dev_wal_replay_emit (not synchronised; the same image, offsets and workspace, untouched in between;
+ * `sizes` as the plan returned them) writes the six output arrays; keys, vals and deleted may have any byte
+ * alignment.  Before it launches it reads the workspace's 128-byte header back (so it waits for what the
+ * stream already holds; nothing, right after the plan): a workspace that does not hold the plan that returned
+ * `sizes` is SEB_ERR_INVALID and nothing is written.  Nothing is launched when records_in == 0. */
+uint64_t seb_dev_wal_replay_workspace_size(uint64_t n);
+int seb_dev_wal_replay_plan(const uint8_t *data, const uint64_t *rec_off, uint64_t n, void *workspace,
+                            uint64_t workspace_bytes, seb_replay_sizes *sizes, void *stream);
+int seb_dev_wal_replay_emit(const uint8_t *data, const uint64_t *rec_off, const seb_replay_sizes *sizes,
+                            const void *workspace, uint64_t workspace_bytes, uint8_t *keys, uint64_t *key_off,
+                            uint8_t *vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq, void *stream);
+/* The host-buffer form on a context: WAL.ReadAll + recoverFromWAL in one synchronous call.  image (bytes) and
+ * the outputs are host memory: seb_wal_scan on the host, H2D, SEB_WAL_VERIFY, plan, emit, D2H.  key_cap /
+ * val_cap bytes and entry_cap entries (key_off and val_off hold entry_cap + 1 offsets, seq is nullable); a
+ * capacity below a size: SEB_ERR_RANGE with *sizes filled, so the caller can retry (the seb_merge convention).
+ * Errors come in ReadAll's order: a complete record that fails verification is SEB_ERR_INVALID and
+ * seb_last_error reads "WAL corruption detected: CRC mismatch (record R)" with the lowest R, also when the tail
+ * is truncated as well (ReadAll meets the bad record first); otherwise a truncated tail is SEB_ERR_SHORT.  An
+ * empty image is valid and gives an empty run. */
+int seb_wal_recover(seb_ctx *ctx, const uint8_t *image, uint64_t bytes, uint8_t *keys, uint64_t key_cap,
+                    uint64_t *key_off, uint8_t *vals, uint64_t val_cap, uint64_t *val_off, uint8_t *deleted,
+                    uint64_t *seq, uint64_t entry_cap, seb_replay_sizes *sizes);
+
 /* ---------- hash-index shard routing + WAL record checksums (off the bloom path) ---- */
 /* shard[i] = FNV-1a32(key i) & ((1 << shard_bits) - 1), the reference's getShard
  * (hashindex/shard.go:47-52; 256 shards = shard_bits 8).  hash[i] (nullable) = the full FNV-1a32.

@@ -6,6 +6,8 @@
 //   seb_filter.cpp    the Go-API filter handle and its CPU fallback
 //   seb_registry.cpp  the registry, MultiGet, the index walk and the block locator
 //   seb_sstable.cpp   the block-search, SSTable-builder and compaction-merge entry points
+//   seb_recover.cpp   the WAL replay's entry points and seb_wal_recover
+//   seb_memtable.cpp  the host half of the WAL replay (no HIP dependency; seb_memtable.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -216,6 +218,7 @@ struct seb_ctx {
     seb::DevBuf sb_bid, sb_pool, sb_blen, sb_cells, sb_out;  // seb_search_blocks: its inputs and outputs on the device
     seb::DevBuf sst_in, sst_ws, sst_out;  // seb_sst_build: the run, the plan's workspace, the three sections
     seb::DevBuf mrg_in, mrg_ws, mrg_out;  // seb_merge: pool + blen + counts, the plan's workspace, the five output arrays
+    seb::DevBuf rpl_in, rpl_ws, rpl_out;  // seb_wal_recover: image + offsets + ok, the plan's workspace, the six output arrays
     seb::PinBuf hkeys, hbits;  // small filter builds: keys in, bits out, read and written by the kernels
     uint64_t chunk_bytes = 64ull << 20;
     std::vector<uint64_t> off_tmp[2];

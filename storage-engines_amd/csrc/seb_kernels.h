@@ -219,6 +219,30 @@ hipError_t merge_ws_check(const void *sizes, const void *ws, uint64_t ws_bytes, 
 hipError_t launch_merge_emit(const uint8_t *pool, const void *sizes, const void *ws, uint8_t *keys, uint64_t *key_off,
                              uint8_t *vals, uint64_t *val_off, uint8_t *deleted, hipStream_t s);
 
+// seb_replay.hip: the WAL replay (lsm/lsm.go:273-298 over lsm/memtable.go:34-93,129-137): the records of a log
+// image into one sorted run, the last record of each key surviving, in the builder's input layout.  The plan
+// lives in a caller-provided workspace: a 128-byte header, then arrays at these offsets, all 16-byte aligned.
+// Tiles are kMergeTile records.
+struct ReplayWs {
+    uint64_t bytes, tiles;
+    uint64_t sums, rec_a, rec_b, cuts;  // per tile x 3, per record x 2, two per tile
+    uint32_t passes;
+};
+ReplayWs replay_ws_layout(uint64_t n);
+uint64_t replay_emit_min_bytes(uint64_t n);  // the least workspace a plan of n records can have
+// n >= 1, n < 2^32, the whole workspace.  Synchronises the stream; sizes_host = one seb_replay_sizes; *err_host =
+// record << 1 | (1: not framed, 0: its offsets decrease) of the least bad record, all ones for none.
+hipError_t launch_replay_plan(const uint8_t *data, const uint64_t *rec_off, uint64_t n, void *ws, void *sizes_host,
+                              uint64_t *err_host, hipStream_t s);
+// *ok = the workspace's header is the plan's that returned `sizes` (one seb_replay_sizes) and its arrays lie
+// inside ws_bytes; reads the header back, so it waits for what the stream holds.
+hipError_t replay_ws_check(const void *sizes, const void *ws, uint64_t ws_bytes, bool *ok, hipStream_t s);
+// sizes: one seb_replay_sizes with records_in >= 1; nothing past its entries_out / key_bytes / val_bytes is
+// written; seq may be null.
+hipError_t launch_replay_emit(const uint8_t *data, const uint64_t *rec_off, const void *sizes, const void *ws, uint8_t *keys,
+                              uint64_t *key_off, uint8_t *vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq,
+                              hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

@@ -60,6 +60,16 @@ class seb_merge_sizes(C.Structure):
         return (self.entries_in, self.entries_out, self.key_bytes, self.val_bytes, self.shadowed, self.dropped)
 
 
+class seb_replay_sizes(C.Structure):
+    _fields_ = [("records_in", C.c_uint64), ("entries_out", C.c_uint64), ("key_bytes", C.c_uint64),
+                ("val_bytes", C.c_uint64), ("overwritten", C.c_uint64), ("tombstones", C.c_uint64),
+                ("max_sequence", C.c_uint64), ("memtable_size", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.records_in, self.entries_out, self.key_bytes, self.val_bytes, self.overwritten, self.tombstones,
+                self.max_sequence, self.memtable_size)
+
+
 class seb_filter_ref(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("num_bits", C.c_uint64), ("num_hashes", C.c_uint32),
                 ("reserved", C.c_uint32)]
@@ -154,6 +164,13 @@ _SIGS = {
     "seb_dev_merge_emit": (_i, [_vp, C.POINTER(seb_merge_sizes), _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_merge": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64,
                        C.POINTER(seb_merge_sizes)]),
+    "seb_wal_replay_plan": (_i, [_vp, _vp, _u64, C.POINTER(seb_replay_sizes)]),
+    "seb_wal_replay_emit": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(seb_replay_sizes)]),
+    "seb_dev_wal_replay_workspace_size": (_u64, [_u64]),
+    "seb_dev_wal_replay_plan": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(seb_replay_sizes), _vp]),
+    "seb_dev_wal_replay_emit": (_i, [_vp, _vp, C.POINTER(seb_replay_sizes), _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_wal_recover": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64,
+                             C.POINTER(seb_replay_sizes)]),
     "seb_workspace_bytes": (_u64, []),
     "seb_dev_or_slices": (_i, [_vp, _u32, _u64, _vp, _vp]),
     "seb_workspace_release": (_i, []),
@@ -403,6 +420,29 @@ class Ctx:
                 err.sizes = sz.as_tuple()
                 raise err
             return _merge_trim(out, sz)
+
+    def wal_recover(self, image, caps: tuple[int, int, int] | None = None):
+        """WAL.ReadAll + recoverFromWAL from host memory: the log image is scanned, verified and replayed.
+        Returns (keys u8, key_off u64, vals u8, val_off u64, deleted u8, seq u64, sizes) of the memtable's
+        sorted run; caps = (key bytes, value bytes, entries) fixes the output capacities instead of retrying
+        with the sizes a too small first call reports.  A record that fails its CRC: SebError (INVALID, "CRC
+        mismatch (record R)"); otherwise a truncated tail: SebError (SHORT)."""
+        img = _wal_image_arg(image)
+        kc, vc, ec = caps if caps is not None else (0, 0, 0)
+        sz = seb_replay_sizes()
+        while True:
+            out = _replay_out(kc, vc, ec)
+            rc = lib().seb_wal_recover(self._p, img.ctypes.data if img.size else None, img.size, out[0].ctypes.data, kc,
+                                       out[1].ctypes.data, out[2].ctypes.data, vc, out[3].ctypes.data, out[4].ctypes.data,
+                                       out[5].ctypes.data, ec, C.byref(sz))
+            if rc == -4 and caps is None and (sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
+                kc, vc, ec = sz.key_bytes, sz.val_bytes, sz.entries_out
+                continue
+            if rc < 0:  # SEB_ERR_RANGE fills the sizes: the exception carries them
+                err = SebError(rc, last_error())
+                err.sizes = sz.as_tuple()
+                raise err
+            return _replay_trim(out, sz)
 
     def probe_multi(self, keys, filters: list[tuple[np.ndarray, int, int]]) -> np.ndarray:
         kb = as_keys(keys)
@@ -1118,6 +1158,94 @@ def merge(pool, blen, run_begin, flags: int = 0, caps=None, device: int = 0):
     ctx = Ctx(device)
     try:
         return ctx.merge(pool, blen, run_begin, flags, caps)
+    finally:
+        ctx.close()
+
+
+# ------------------------------- WAL replay (lsm/lsm.go:273-298 over lsm/memtable.go:34-93,129-137)
+
+def _wal_image_arg(image) -> np.ndarray:
+    if isinstance(image, (bytes, bytearray, memoryview)):
+        return np.frombuffer(image, np.uint8)
+    return np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+
+
+def _replay_host_args(image, rec_off):
+    img = _wal_image_arg(image)
+    off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    return img, off, max(off.size - 1, 0)
+
+
+def _replay_out(key_bytes: int, val_bytes: int, entries: int):
+    return _merge_out(key_bytes, val_bytes, entries) + (np.zeros(max(entries, 1), np.uint64),)
+
+
+def _replay_trim(out, sz):
+    n = sz.entries_out
+    return (out[0][: sz.key_bytes], out[1][: n + 1], out[2][: sz.val_bytes], out[3][: n + 1], out[4][:n], out[5][:n],
+            sz.as_tuple())
+
+
+def wal_replay_plan(image, rec_off) -> tuple[int, int, int, int, int, int, int, int]:
+    """The host half's plan: (records_in, entries_out, key_bytes, val_bytes, overwritten, tombstones,
+    max_sequence, memtable_size) of the replay of records [rec_off[i], rec_off[i+1]) of the image.  A record
+    that is not framed, or offsets that decrease: SebError (INVALID) naming the record."""
+    img, off, n = _replay_host_args(image, rec_off)
+    sz = seb_replay_sizes()
+    check(lib().seb_wal_replay_plan(img.ctypes.data if n else None, off.ctypes.data if n else None, n, C.byref(sz)))
+    return sz.as_tuple()
+
+
+def wal_replay_emit(image, rec_off, sizes=None):
+    """The host half: (keys u8, key_off u64, vals u8, val_off u64, deleted u8, seq u64, sizes) of the memtable's
+    sorted run; sizes default to wal_replay_plan's."""
+    img, off, n = _replay_host_args(image, rec_off)
+    sz = seb_replay_sizes(*(wal_replay_plan(img, off) if sizes is None else sizes))
+    out = _replay_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
+    check(lib().seb_wal_replay_emit(img.ctypes.data if n else None, off.ctypes.data if n else None, n, out[0].ctypes.data,
+                                    out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, out[4].ctypes.data,
+                                    out[5].ctypes.data, C.byref(sz)))
+    return _replay_trim(out, sz)
+
+
+def dev_wal_replay_workspace_size(n: int) -> int:
+    return lib().seb_dev_wal_replay_workspace_size(n)
+
+
+def dev_wal_replay_plan(data, rec_off, ws, ws_bytes: int | None = None, stream=None):
+    """Device form: data (u8 tensor or view, any alignment) and rec_off (n + 1 offsets, a 64-bit tensor) on the
+    device; checks, decodes and sorts the records and marks the survivors into the workspace tensor `ws`
+    (dev_wal_replay_workspace_size bytes); synchronises and returns the sizes."""
+    n = max(rec_off.numel() - 1, 0) if rec_off is not None else 0
+    sz = seb_replay_sizes()
+    check(lib().seb_dev_wal_replay_plan(_ptr(data) if n else None, _ptr(rec_off) if n else None, n, _ptr(ws),
+                                        (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes,
+                                        C.byref(sz), _stream(stream)))
+    return sz.as_tuple()
+
+
+def dev_wal_replay_emit(data, rec_off, sizes, ws, keys, key_off, vals, val_off, deleted, seq=None, stream=None) -> None:
+    """Device form: writes the run (sizes as dev_wal_replay_plan returned them): keys / vals (u8), key_off /
+    val_off (entries_out + 1 u64 each), deleted (entries_out u8), seq (entries_out u64, optional).  Not
+    synchronised."""
+    sz = seb_replay_sizes(*sizes)
+    for name, t, size in (("keys", keys, sz.key_bytes), ("vals", vals, sz.val_bytes), ("deleted", deleted, sz.entries_out),
+                          ("key_off", key_off, 8 * (sz.entries_out + 1)), ("val_off", val_off, 8 * (sz.entries_out + 1)),
+                          ("seq", seq, 8 * sz.entries_out if seq is not None else 0)):
+        if (t is None and size) or (t is not None and _nbytes(t) < size):
+            raise ValueError(f"{name} holds {0 if t is None else _nbytes(t)} bytes, the plan needs {size}")
+    if sz.records_in and (rec_off is None or rec_off.numel() < sz.records_in + 1):
+        raise ValueError(f"rec_off holds fewer than {sz.records_in + 1} offsets")
+    check(lib().seb_dev_wal_replay_emit(_ptr(data), _ptr(rec_off), C.byref(sz), _ptr(ws), _nbytes(ws) if ws is not None else 0,
+                                        _ptr(keys), _ptr(key_off), _ptr(vals), _ptr(val_off), _ptr(deleted), _ptr(seq),
+                                        _stream(stream)))
+
+
+def wal_recover(image, caps=None, device: int = 0):
+    """Ctx.wal_recover on a context made for the call."""
+    ctx = Ctx(device)
+    try:
+        return ctx.wal_recover(image, caps)
     finally:
         ctx.close()
 
