@@ -5,12 +5,24 @@ seb_merge_emit, itself held to the restatements in test_merge.py) byte for byte:
 makes the merge tree lopsided), run lengths around the merge tile T, ties in every run and across a tile
 boundary of the last pass, Go string order on keys that tie in their first 16 and 40 bytes, tombstones, and
 the pool's layouts.  Outputs start as 0xA5 between guard bytes and sit at odd addresses.  The merged run goes
-straight into the device builder, whose files equal the restatement's."""
+straight into the device builder, whose files equal the restatement's.
+
+Beyond six tiles, 135 blocks and 9 runs (each test asserts by arithmetic that its shape crosses its threshold,
+and compares the device with the host half and with rule_merge or scale_ref's lexsort):
+  pools of 255, 256, 257, 513 blocks     a non-zero group base in k_merge_spread; a run boundary at blocks 255,
+                                         256 and 257; blocks without entries at 255, 256 and the pool's end
+  16, 17, 33, 257, 1025 runs             pairs of 8 to 1024 runs, lopsided trees, every tenth run empty, a second
+                                         workgroup of k_merge_runs; an unsorted run 600 behind two empty runs
+  17 runs, some 139 tiles                a second workgroup of k_merge_cuts
+  5 runs, more than 1024 tiles           the carry of k_merge_scan over the tiles' sums
+The carry of the same k_merge_scan over the group sums needs more than 262,144 blocks, a pool of 1 GiB: it is
+not run here."""
 import numpy as np
 import pytest
 
 import block_ref as br
 import merge_ref as mr
+import scale_ref as sc
 import sstable_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -44,14 +56,16 @@ def dev_pool(torch, pool, blen):
     return dpool, dblen
 
 
-def device_plan(torch, seb, pool, blen, rb, flags=0):
-    """count + plan on the device: (dpool, ws, sizes); the counts are checked against loadBlock's."""
+def device_plan(torch, seb, pool, blen, rb, flags=0, block_counts=None):
+    """count + plan on the device: (dpool, ws, sizes); the counts are checked against loadBlock's, or against
+    block_counts where a generator states them."""
     nb = len(blen)
     dpool, dblen = dev_pool(torch, pool, blen)
     bc, dcnt = guarded(torch, 2 * nb)
     run_entries = seb.dev_merge_count(dpool, dblen, rb, dcnt.view(torch.int16))
     counts = np.frombuffer(check_guards(bc, 2 * nb).tobytes(), np.uint16).tolist()
-    want = [len(mr.load_block(bytes(pool[b * 4096:b * 4096 + min(int(blen[b]), 4096)]))) for b in range(nb)]
+    want = block_counts if block_counts is not None else \
+        [len(mr.load_block(bytes(pool[b * 4096:b * 4096 + min(int(blen[b]), 4096)]))) for b in range(nb)]
     assert counts == want
     assert run_entries == [sum(want[rb[r]:rb[r + 1]]) for r in range(len(rb) - 1)]
     n = sum(run_entries)
@@ -82,16 +96,21 @@ def device_emit(torch, seb, dpool, ws, sizes):
 
 def compare(torch, seb, runs, flags=0, name="", **kw):
     """Device against host half over runs of block images; returns the merged items and the sizes."""
-    pool, blen, rb = mr.pool_of(runs, **kw)
+    got, sizes = compare_pool(torch, seb, *mr.pool_of(runs, **kw), flags, name)
+    return mr.unpack(*got), sizes
+
+
+def compare_pool(torch, seb, pool, blen, rb, flags=0, name="", block_counts=None):
+    """Device against host half over a pool: the device's five arrays, read back once, and the sizes."""
     want = seb.merge_emit(pool, blen, rb, flags)
-    dpool, ws, sizes = device_plan(torch, seb, pool, blen, rb, flags)
+    dpool, ws, sizes = device_plan(torch, seb, pool, blen, rb, flags, block_counts)
     assert sizes == want[5], (name, "sizes")
     got = device_emit(torch, seb, dpool, ws, sizes)
     for j, what in enumerate(("keys", "key_off", "vals", "val_off", "deleted")):
         if not np.array_equal(got[j], want[j]):
             at = int(np.nonzero(got[j][:len(want[j])] != want[j][:len(got[j])])[0][0])
             raise AssertionError(f"{name}: {what} differs first at {at}: {got[j][at:at + 8]} != {want[j][at:at + 8]}")
-    return mr.unpack(*got), sizes
+    return got, sizes
 
 
 def items_of(keys, r, rng=None, dels=0.0):
@@ -254,6 +273,102 @@ def test_value_sizes_and_pool_layout(seb, torch_cuda, full_blen):
     got, sizes = compare(torch_cuda, seb, runs, 0, f"layout full_blen={full_blen}", full_blen=full_blen, fill=0xEE)
     assert sizes[0] == len(big) + len(none) + len(mixed)
     assert got == mr.as_bytes(mr.rule_merge(mr.decoded(runs)))
+
+
+# ------------------------------------------------------------------ many blocks, many runs, many tiles
+
+def passes_of(nruns):
+    p = 0
+    while (1 << p) < nruns:
+        p += 1
+    return p
+
+
+def check_closed_form(got, sizes, want, name):
+    arrays, want_sizes = want
+    assert sizes == want_sizes, (name, sizes, want_sizes)
+    for j, what in enumerate(("keys", "key_off", "vals", "val_off", "deleted")):
+        assert np.array_equal(got[j], arrays[j]), (name, what, "differs from the closed form")
+
+
+@pytest.mark.parametrize("nb,bounds", sc.GROUP_POOLS, ids=[f"{nb}-{b[2]}" for nb, b in sc.GROUP_POOLS])
+def test_block_groups(seb, torch_cuda, nb, bounds):
+    """Pools of 255, 256, 257 and 513 blocks, a group of the first[] scan being 256: k_merge_spread adds a
+    non-zero group base from block 256 on; a run boundary at blocks 255, 256 and 257 makes rf[] read first[] just
+    before, at and just after a group edge; blocks 255, 256 and the last hold no entries."""
+    groups = -(-nb // 256)
+    assert groups == {255: 1, 256: 1, 257: 2, 513: 3}[nb] and (nb <= 256 or nb > 256 and groups >= 2)
+    if nb == 513:
+        assert nb // 256 >= 2 and bounds[2] in (255, 256, 257)
+    runs = sc.group_runs(nb, bounds)
+    flat = [img for run in runs for img in run]
+    assert len(flat) == nb and all(len(mr.load_block(flat[b])) == (0 if b in (255, 256, nb - 1) else 3) for b in range(nb))
+    ents = mr.decoded(runs)
+    for flags in (0, seb.MERGE_DROP_TOMBSTONES):
+        got, sizes = compare(torch_cuda, seb, runs, flags, f"{nb} blocks, flags {flags}", fill=0xCC)  # counts against load_block
+        assert got == mr.as_bytes(mr.rule_merge(ents, bool(flags))) and sizes[4] > 0
+
+
+@pytest.mark.parametrize("nruns", [16, 17, 33, 257, 1025])
+def test_many_runs(seb, torch_cuda, nruns):
+    """16 to 1025 runs of 0 to 20 entries, every tenth run empty: pairs of 8, 16, ... 1024 runs (merge_tile and the
+    host's tile table), a lopsided tree (17, 33, 257, 1025), rf[] with equal neighbours, and from 256 runs on a
+    second workgroup of k_merge_runs."""
+    passes = passes_of(nruns)
+    assert passes >= 4 and (1 << (passes - 1)) >= (16 if nruns > 16 else 8)  # the widest pair's side, in runs
+    if nruns > 256:
+        assert (nruns + 1 + 255) // 256 >= 2  # k_merge_runs: a lane per rf[0 .. nruns]
+    blocks = [mr.run_blocks(run) for run in sc.many_runs(nruns)]
+    assert sum(not run for run in blocks) >= nruns // 10 and not blocks[9]
+    ents = mr.decoded(blocks)
+    for flags in (0, seb.MERGE_DROP_TOMBSTONES):
+        got, sizes = compare(torch_cuda, seb, blocks, flags, f"{nruns} runs, flags {flags}")
+        assert got == mr.as_bytes(mr.rule_merge(ents, bool(flags))) and sizes[4] > 0
+        assert (sizes[5] > 0) == bool(flags)
+
+
+def test_unsorted_run_above_256_is_refused(seb, torch_cuda):
+    """Run 600 of 1025 is not increasing at its entry 5 and runs 598 and 599 are empty: k_merge_check's bisection
+    over rf[] must land on run 600, not on an empty run with the same first record.  Run 900 is bad as well."""
+    bad = 600
+    assert bad > 256
+    runs = [list(run) for run in sc.many_runs(1025)]
+    runs[bad - 2] = []
+    assert not runs[bad - 1] and not runs[bad - 2]
+    for r, at in ((bad, 5), (900, 3)):
+        run = [(key8(7 * i), b"bad%d" % r, 0) for i in range(12)]
+        run[at - 1], run[at] = run[at], run[at - 1]
+        runs[r] = run
+    pool, blen, rb = mr.pool_of([mr.run_blocks(run) for run in runs])
+    with pytest.raises(seb.SebError) as host:
+        seb.merge_plan(pool, blen, rb)
+    with pytest.raises(seb.SebError) as ei:
+        device_plan(torch_cuda, seb, pool, blen, rb)
+    assert ei.value.code == -1 and f"run {bad} entry 5 " in str(ei.value), str(ei.value)
+    assert str(ei.value).split(": ", 2)[2] == str(host.value).split(": ", 2)[2]
+
+
+@pytest.mark.parametrize("flags", [0, 1], ids=["keep", "drop_tombstones"])
+def test_cuts_second_workgroup(seb, torch_cuda, flags):
+    """17 runs over some 139 tiles: the last passes have more than 128 tiles, so k_merge_cuts' searches, a lane
+    each, fill more than one workgroup of 256."""
+    pool, blen, rb, want = sc.merge_pool(140 * T, 17, 400_000)
+    n = want[flags][1][0]
+    assert 2 * (-(-n // T)) > 256 and passes_of(17) == 5 and len(blen) // 256 >= 2
+    got, sizes = compare_pool(torch_cuda, seb, pool, blen, rb, flags, "139 tiles", ((blen.astype(np.int64) - 4) // 21).tolist())
+    check_closed_form(got, sizes, want[flags], "139 tiles")
+
+
+@pytest.mark.parametrize("flags", [0, 1], ids=["keep", "drop_tombstones"])
+def test_scan_carry_over_more_than_1024_tiles(seb, torch_cuda, flags):
+    """5 runs of some 210,000 entries: more than 1024 tiles go into the survivor scan, so k_merge_scan's second
+    chunk takes the first chunk's sum as its carry (counts, key bytes, value bytes); 21 groups of blocks."""
+    pool, blen, rb, want = sc.merge_pool(1024 * T + 40_000, 5, 3_000_000)
+    n = want[flags][1][0]  # entries in, after each run's draws lost their duplicates
+    assert -(-n // T) > 1024 and len(blen) // 256 >= 2
+    got, sizes = compare_pool(torch_cuda, seb, pool, blen, rb, flags, "1026 tiles", ((blen.astype(np.int64) - 4) // 21).tolist())
+    assert sizes[0] == n
+    check_closed_form(got, sizes, want[flags], "more than 1024 tiles")
 
 
 # ------------------------------------------------------------------ errors

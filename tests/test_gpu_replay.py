@@ -7,11 +7,21 @@ descending and random order, a key's records in tiles 0, 2 and 4, an equal-key g
 sorted result, Go string order on keys that tie in their first 16 and 40 bytes, Delete then Put and the reverse,
 and large keys and values.  Outputs start as 0xA5 between guard bytes; keys, values and deleted sit at odd
 addresses, the image sits at an odd address, and a 0x5A guard follows the workspace.  The replayed run goes
-straight into the device builder, whose file equals the restatement's."""
+straight into the device builder, whose file equals the restatement's.
+
+Beyond six tiles (each test asserts by arithmetic that its shape crosses its threshold, and compares the device
+with the host half and with a reference of its own: last-record-wins by a dict, or scale_ref's lexsort):
+  8 T + 1, 16 T, 17 T - 5, 33 T + 1 records    merge widths of 8 T and more, lopsided trees at depth; long
+                                               equal-key groups, then mostly distinct keys
+  17 T, one key's 2 T + 5 records in all tiles  a group over more than two whole tiles, ended by a Delete with a value
+  129 T + 3 records                             130 tiles: a second workgroup of k_replay_cuts; bad framing of
+                                               records 129 T + 1 and 129 T + 2 names the first, in the host's words
+  1024 T + 1025 records                         1026 tiles, 11 passes: the carry of k_replay_scan"""
 import numpy as np
 import pytest
 
 import memtable_ref as mref
+import scale_ref as sc
 import sstable_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +54,7 @@ def dev_image(torch, image, off, lead=7):
     buf = torch.from_numpy(np.concatenate([np.full(lead, 0xEE, np.uint8), img])).cuda()
     view = buf[lead:]
     assert len(img) == 0 or view.data_ptr() % 2 == 1
-    doff = torch.from_numpy(np.asarray(off, np.uint64).view(np.int64)).cuda()
+    doff = torch.from_numpy(np.array(off, np.uint64).view(np.int64)).cuda()
     return view, doff
 
 
@@ -77,9 +87,8 @@ def device_emit(torch, seb, dimg, doff, ws, sizes):
             u64(check_guards(bvo, 8 * (n_out + 1))), check_guards(bd, n_out, GUARD + 5), u64(check_guards(bs, 8 * n_out)))
 
 
-def compare(torch, seb, recs, name="", ref=True):
-    """Device against host half over a log of records; returns the replayed entries and the sizes."""
-    image, off = mref.wal_image(recs)
+def compare_image(torch, seb, image, off, name=""):
+    """Device against host half over a log image: the device's six arrays, read back once, and the sizes."""
     want = seb.wal_replay_emit(image, off)
     dimg, doff, ws, sizes = device_plan(torch, seb, image, off)
     assert sizes == want[6], (name, "sizes", sizes, want[6])
@@ -88,6 +97,13 @@ def compare(torch, seb, recs, name="", ref=True):
         if not np.array_equal(got[j], want[j]):
             at = int(np.nonzero(got[j][:len(want[j])] != want[j][:len(got[j])])[0][0])
             raise AssertionError(f"{name}: {what} differs first at {at}: {got[j][at:at + 8]} != {want[j][at:at + 8]}")
+    return got, sizes
+
+
+def compare(torch, seb, recs, name="", ref=True):
+    """Device against host half over a log of records; returns the replayed entries and the sizes."""
+    image, off = mref.wal_image(recs)
+    got, sizes = compare_image(torch, seb, image, off, name)
     ents = mref.unpack(*got)
     if ref:  # the restatement itself, where its sorted-slice inserts stay quick
         assert (ents, sizes) == mref.expected(recs), name
@@ -201,7 +217,97 @@ def test_value_sizes_and_one_large_key_and_value(seb, torch_cuda):
     assert ks[at:at + 3] == [big + b"a", big + b"b", big + b"c"]
 
 
+# ------------------------------------------------------------------ many tiles
+
+def passes_of(n):
+    """The levels of the pairwise merge tree over the tiles of n records."""
+    tiles, p = -(-n // T), 0
+    while (1 << p) < tiles:
+        p += 1
+    return tiles, p
+
+
+def check_closed_form(got, sizes, want, want_sizes, name):
+    assert sizes == want_sizes, (name, sizes, want_sizes)
+    for j, what in enumerate(("keys", "key_off", "vals", "val_off", "deleted", "seq")):
+        assert np.array_equal(got[j], want[j]), (name, what, "differs from the closed form")
+
+
+@pytest.mark.parametrize("distinct", [0, 1], ids=["few_keys", "distinct_keys"])
+@pytest.mark.parametrize("n", [8 * T + 1, 16 * T, 17 * T - 5, 33 * T + 1])
+def test_pass_tree_depth(seb, torch_cuda, n, distinct):
+    """9, 16, 17 and 34 tiles: merge widths of 8 T and more, and trees whose last pair is one short tile (8 T + 1,
+    33 T + 1) or a lopsided subtree (17 T - 5) against a full power of two.  Variable-length records: long
+    equal-key groups, then mostly distinct keys.  Against the host half and against last-record-wins by a dict."""
+    tiles, passes = passes_of(n)
+    assert tiles in (9, 16, 17, 34) and passes >= 4 and (T << (passes - 1)) >= 8 * T  # a pass of width >= 8 T runs
+    recs, image, off, want, want_sizes = sc.deep_log(n, distinct)
+    got, sizes = compare_image(torch_cuda, seb, image, off, f"n={n}")
+    assert sizes == want_sizes and mref.unpack(*got) == want
+    assert (sizes[1] > n // 2) == bool(distinct) and sizes[5] > 0
+
+
+def test_one_keys_group_over_more_than_two_tiles_at_depth(seb, torch_cuda):
+    """17 tiles; one key holds 2 T + 5 records, some in every tile, so its group spans more than two whole tiles of
+    the sorted records and every pass merges parts of it.  Its last record is a Delete that carries value bytes."""
+    n, m = 17 * T, 2 * T + 5
+    tiles, passes = passes_of(n)
+    assert tiles == 17 and passes == 5 and m > 2 * T
+    rng = np.random.default_rng(17)
+    hot = key8(500000)  # sorts into the middle of the fillers
+    recs = [(key8(2 * int(i) + 1), b"f%d" % i, 3 * s, int(s % 9 == 0)) for s, i in enumerate(rng.permutation(n))]
+    per = [m // 17 + (t < m % 17) for t in range(17)]
+    at = sorted(t * T + int(x) for t in range(17) for x in rng.choice(T, per[t], replace=False))
+    assert len(at) == m and {a // T for a in at} == set(range(17))
+    for j, a in enumerate(at):
+        recs[a] = (hot, b"hot%d" % j, 10 ** 7 + 5 * j, 1 if j % 7 == 3 else 0)
+    recs[at[-1]] = (hot, b"carried-by-the-delete", 77, 1)
+    want, want_sizes = sc.last_wins(recs)
+    got, sizes = compare(torch_cuda, seb, recs, "one key over 17 tiles", ref=False)
+    assert (got, sizes) == (want, want_sizes)
+    assert [e for e in got if e[0] == hot] == [(hot, b"", 1, 77)]
+    assert sizes[1] == n - m + 1 and sizes[4] == m - 1 and sizes[6] == 10 ** 7 + 5 * (m - 2)
+
+
+def test_cuts_second_workgroup(seb, torch_cuda):
+    """130 tiles: 260 diagonal searches a pass, a lane each, 256 lanes to a workgroup of k_replay_cuts."""
+    n = 129 * T + 3
+    tiles, passes = passes_of(n)
+    assert 2 * tiles > 256 and passes == 8
+    image, off, want, want_sizes = sc.replay_log(n, 50_000)
+    got, sizes = compare_image(torch_cuda, seb, image, off, "130 tiles")
+    check_closed_form(got, sizes, want, want_sizes, "130 tiles")
+
+
+def test_scan_carry_over_more_than_1024_tiles(seb, torch_cuda):
+    """1026 tiles, 11 passes: k_replay_scan's second chunk takes the first chunk's sum as its carry, for the
+    survivors' counts, key bytes and value bytes."""
+    n = 1024 * T + 1025
+    tiles, passes = passes_of(n)
+    assert tiles > 1024 and -(-n // T) == 1026 and passes == 11
+    image, off, want, want_sizes = sc.replay_log(n, 400_000)
+    got, sizes = compare_image(torch_cuda, seb, image, off, "1026 tiles")
+    check_closed_form(got, sizes, want, want_sizes, "1026 tiles")
+
+
 # ------------------------------------------------------------------ errors
+
+def test_bad_framing_far_from_tile_0(seb, torch_cuda):
+    """Records 129 T + 1 and 129 T + 2, in the last of 130 tiles, are not framed: the lowest is named, in the host's words."""
+    n = 129 * T + 3
+    bad = 129 * T + 1
+    assert bad // T >= 128 and bad + 1 < n
+    image, off, _, _ = sc.replay_log(n, 50_000)
+    img = image.copy()
+    img[int(off[bad]) + 16] ^= 2  # valueSize: 21 + keySize + valueSize != the record's length
+    img[int(off[bad + 1]) + 12] ^= 1  # and the next record's keySize
+    with pytest.raises(seb.SebError) as host:
+        seb.wal_replay_plan(img, off)
+    with pytest.raises(seb.SebError) as ei:
+        device_plan(torch_cuda, seb, img, off)  # checks the guard behind the workspace
+    assert ei.value.code == -1 and f"record {bad} " in str(ei.value), str(ei.value)
+    assert str(ei.value).split(": ", 2)[2] == str(host.value).split(": ", 2)[2]
+
 
 @pytest.mark.parametrize("bad", [0, 1500, 2 * T + 99])
 def test_bad_framing(seb, torch_cuda, bad):

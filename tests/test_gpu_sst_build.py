@@ -6,7 +6,15 @@ file boundaries at 0-entry and 1-entry files and inside a block's worth of entri
 T + 1 entries for the cut's tile size T, odd data pointers, offsets[0] != 0 and the fixed 16-byte-stride
 layout.  Outputs start as 0xA5 between guard bytes: the padding must come out zero and the guards
 untouched.  seb_sst_build gives the restatement's whole file image, and the files it writes serve the
-read side (registry, locate, block search, resolve) end to end."""
+read side (registry, locate, block search, resolve) end to end.
+
+Beyond four tiles and 45 files (each test asserts by arithmetic that its shape crosses its threshold):
+  65, 257, 1025, 1500 files over four tiles   a second workgroup of k_sst_walk and k_sst_filemeta (64 files each),
+                                              of k_sst_files and k_sst_sizes (256), the carry of the meta_len scan
+  40 tiles cut into 300 files                 files over several tiles, tiles with several files: k_sst_walk's hops
+  1024 T + 1025 entries, one and three files  1026 tiles: the carry of k_sst_scan; against the host half and
+                                              against scale_ref's closed form
+The 16 bytes behind the workspace stay 0x5A through plan and encode."""
 import ctypes as C
 import struct
 
@@ -15,6 +23,7 @@ import pytest
 
 import block_ref as br
 import keygen as kg
+import scale_ref as sc
 import sstable_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -36,12 +45,18 @@ def dev_run(torch, seb, items, layout):
     16-byte stride without an offset array."""
     if layout == "fixed16":
         assert all(len(k) == 16 for k, _, _ in items)
-        kd, koff, vd, voff, dl = sr.pack(items)
-        dk = seb.dev_keys(torch.from_numpy(np.concatenate([kd, np.zeros(16, np.uint8)])).cuda(), n=len(items), stride=16)
+        return dev_packed(torch, seb, sr.pack(items), layout)
+    kp, vp = (3, 5) if layout == "odd" else (0, 0)
+    return dev_packed(torch, seb, sr.pack(items, key_pad=kp, val_pad=vp), layout)
+
+
+def dev_packed(torch, seb, packed, layout):
+    """dev_run over sstable_ref.pack's five arrays (the pads already in them)."""
+    kd, koff, vd, voff, dl = packed
+    if layout == "fixed16":
+        dk = seb.dev_keys(torch.from_numpy(np.concatenate([kd, np.zeros(16, np.uint8)])).cuda(), n=len(dl), stride=16)
         dv = torch.from_numpy(np.concatenate([vd, np.zeros(1, np.uint8)])).cuda()
     else:
-        kp, vp = (3, 5) if layout == "odd" else (0, 0)
-        kd, koff, vd, voff, dl = sr.pack(items, key_pad=kp, val_pad=vp)
         lead = 1 if layout == "odd" else 0
         k = torch.from_numpy(np.concatenate([np.full(lead, 0xEE, np.uint8), kd, np.full(3, 0xEE, np.uint8)])).cuda()[lead:]
         dv = torch.from_numpy(np.concatenate([np.full(lead, 0xDD, np.uint8), vd, np.full(3, 0xDD, np.uint8)])).cuda()[lead:]
@@ -63,48 +78,65 @@ def check_guards(buf, size, lead=GUARD):
     return h[lead:lead + size].tobytes()
 
 
-def device_sections(torch, seb, items, file_begin, layout):
-    """Plan + encode on the device: (sizes per file, data, blen, index, metadata)."""
-    dk, dv, dvoff, ddel = dev_run(torch, seb, items, layout)
+def device_sections(torch, seb, items, file_begin, layout, packed=None):
+    """Plan + encode on the device: (sizes per file, data, blen, index, metadata); the run as items, or as
+    sstable_ref.pack's arrays."""
+    dk, dv, dvoff, ddel = dev_run(torch, seb, items, layout) if packed is None else dev_packed(torch, seb, packed, layout)
     nf = len(file_begin) - 1
-    ws = torch.full((seb.dev_sst_workspace_size(len(items), nf) + 16,), 0x5A, dtype=torch.uint8, device="cuda")
-    sizes = seb.dev_sst_plan(dk, dvoff, file_begin, ws)
+    ws = torch.full((seb.dev_sst_workspace_size(dk.n, nf) + 16,), 0x5A, dtype=torch.uint8, device="cuda")
+    sizes = seb.dev_sst_plan(dk, dvoff, file_begin, ws[:-16])
     blocks, d, x, m = (sum(s[j] for s in sizes) for j in range(4))
     bd, data = guarded(torch, d)
     assert data.data_ptr() % 16 == 0
     bx, index = guarded(torch, x, lead=GUARD + 1)  # the index and the metadata at odd addresses
     bm, meta = guarded(torch, m, lead=GUARD + 3)
     bl, blen = guarded(torch, 2 * blocks)
-    seb.dev_sst_encode(dk, dv, dvoff, ddel, file_begin, sizes, ws, data, index, meta, blen=blen.view(torch.int16))
+    seb.dev_sst_encode(dk, dv, dvoff, ddel, file_begin, sizes, ws[:-16], data, index, meta, blen=blen.view(torch.int16))
     torch.cuda.synchronize()
+    assert (ws[-16:].cpu().numpy() == 0x5A).all(), "the plan or the encode wrote past the workspace"
     return (sizes, check_guards(bd, d), np.frombuffer(check_guards(bl, 2 * blocks), np.uint16).tolist(),
             check_guards(bx, x, GUARD + 1), check_guards(bm, m, GUARD + 3))
 
 
 def host_sections(seb, items, file_begin):
     """The host half per file, concatenated the way the device lays the files out."""
-    sizes, data, index, meta, blens = [], b"", b"", b"", []
+    sizes, data, index, meta, blens = [], [], [], [], []
     for f in range(len(file_begin) - 1):
         part = items[file_begin[f]:file_begin[f + 1]]
         kd, koff, vd, voff, dl = sr.pack(part)
         sizes.append(seb.sst_plan((kd, koff), voff))
         d, x, m = seb.sst_encode((kd, koff), vd, voff, dl)
-        data, index, meta = data + d, index + x, meta + m
+        data.append(d), index.append(x), meta.append(m)
         blens += sr.sections(part)[3]
-    return sizes, data, blens, index, meta
+    return sizes, b"".join(data), blens, b"".join(index), b"".join(meta)
+
+
+def host_sections_packed(seb, run, file_begin):
+    """host_sections over a scale_ref.sst_run; the true block lengths are not the host half's to give."""
+    sizes, data, index, meta = [], [], [], []
+    for lo, hi in zip(file_begin[:-1], file_begin[1:]):
+        kd, koff, vd, voff, dl = sc.sst_slice(run, lo, hi)
+        sizes.append(seb.sst_plan((kd, koff), voff))
+        d, x, m = seb.sst_encode((kd, koff), vd, voff, dl)
+        data.append(d), index.append(x), meta.append(m)
+    return sizes, b"".join(data), None, b"".join(index), b"".join(meta)
 
 
 def compare(torch, seb, items, file_begin, layout, name=""):
     want = host_sections(seb, items, file_begin)
     got = device_sections(torch, seb, items, file_begin, layout)
+    check_sections(got, want, layout, name)
+    return want[0]
+
+
+def check_sections(got, want, layout, name):
     assert got[0] == want[0], (name, "sizes")
-    assert got[2] == want[2], (name, "blen")
+    assert want[2] is None or got[2] == want[2], (name, "blen")
     for j, what in ((1, "data"), (3, "index"), (4, "metadata")):
         if got[j] != want[j]:
             at = next(i for i, (a, b) in enumerate(zip(got[j], want[j])) if a != b)
             raise AssertionError(f"{name} {layout}: {what} differs first at byte {at} (block {at // 4096}, +{at % 4096}): "
                                  f"{got[j][at:at + 8].hex()} != {want[j][at:at + 8].hex()}")
-    return want[0]
 
 
 DEVICE_SHAPES = [(n, it) for n, it in sr.shapes() if not n.endswith("_over") and n != "none"]
@@ -155,6 +187,65 @@ def test_many_files_random(seb, torch_cuda):
     compare(torch, seb, big, [0, 700, 1300], "even", "big entries")
     tiny = [(b"", b"", i % 2) for i in range(3000)]  # 454 entries per block: the longest hops between block starts
     compare(torch, seb, tiny, [0, 455, 3000], "odd", "empty entries")
+
+
+@pytest.mark.parametrize("nf", [65, 257, 1025, 1500])
+def test_file_counts(seb, torch_cuda, nf):
+    """More files than a workgroup of the per-file kernels has lanes: 64 for k_sst_walk and k_sst_filemeta, 256 for
+    k_sst_files and k_sst_sizes, and more than 1024 for the carry of the meta_len scan.  Some 4,000 entries over
+    four tiles; files that end before, at and after a tile edge, empty and one-entry files among them."""
+    T = seb.SST_TILE
+    assert (nf + 63) // 64 >= 2  # every nf: k_sst_walk, k_sst_filemeta
+    assert (nf + 255) // 256 >= 2 or nf == 65  # k_sst_files, k_sst_sizes
+    assert nf > 1024 or nf in (65, 257)  # the meta_len scan's second chunk
+    rng = np.random.default_rng(nf)
+    items = sr.random_items(rng, 4000)
+    n = len(items)
+    assert 3 * T + 1 < n <= 4000
+    cuts = [T - 1, T, T + 1, 2 * T, 2 * T, 2 * T + 1, 3 * T - 1, 3 * T - 1, 3 * T + 1, n]
+    cuts += [int(c) for c in rng.integers(0, n + 1, nf - 1 - len(cuts))]
+    fb = [0] + sorted(cuts) + [n]
+    lens = [b - a for a, b in zip(fb[:-1], fb[1:])]
+    assert len(fb) == nf + 1 and 0 in lens and 1 in lens and lens[-1] == 0
+    want = host_sections(seb, items, fb)
+    ref = [sr.sections(items[a:b]) for a, b in zip(fb[:-1], fb[1:])]
+    assert want[1] == b"".join(r[0] for r in ref) and want[3] == b"".join(r[1] for r in ref)
+    assert want[4] == b"".join(r[2] for r in ref) and want[0] == [(len(r[3]), len(r[0]), len(r[1]), len(r[2]), 0) for r in ref]
+    for layout in ("odd", "even"):
+        check_sections(device_sections(torch_cuda, seb, items, fb, layout), want, layout, f"{nf} files")
+
+
+def test_many_tiles_and_many_files(seb, torch_cuda):
+    """40 tiles cut into 300 files at random places: files that span several tiles (k_sst_walk's lane hops from
+    exit to exit) and tiles that hold several files (their lanes write the same entry point)."""
+    T = seb.SST_TILE
+    rng = np.random.default_rng(40)
+    n = 40 * T
+    items = small_items(rng, n)
+    # 40 cuts anywhere, 259 crowded into six of the tiles: long files between the crowds, many files to a tile in them
+    crowd = np.concatenate([rng.integers(10 * T, 12 * T, 100), rng.integers(25 * T, 29 * T, 159)])
+    fb = [0] + sorted(int(c) for c in np.concatenate([rng.integers(0, n + 1, 40), crowd])) + [n]
+    lens = [b - a for a, b in zip(fb[:-1], fb[1:])]
+    tiles_of = [(b - 1) // T - a // T + 1 for a, b in zip(fb[:-1], fb[1:]) if b > a]
+    assert len(lens) == 300 and (300 + 63) // 64 >= 2 and max(tiles_of) >= 3 and max(lens) > 2 * T
+    assert max(np.bincount([c // T for c in fb[1:-1]], minlength=40)) >= 3 and n // T == 40
+    want = host_sections(seb, items, fb)
+    check_sections(device_sections(torch_cuda, seb, items, fb, "odd"), want, "odd", "40 tiles, 300 files")
+
+
+@pytest.mark.parametrize("files", [1, 3])
+def test_scan_carry_over_more_than_1024_tiles(seb, torch_cuda, files):
+    """1026 tiles: k_sst_scan's second chunk takes the first chunk's sum as its carry, for the tiles' block counts
+    and index bytes.  One file, and three files cut at entries that are no multiple of the tile."""
+    T = seb.SST_TILE
+    n = 1024 * T + 1025
+    assert -(-n // T) > 1024
+    fb = [0, n] if files == 1 else [0, 300 * T + 77, 301 * T - 5, n]
+    assert all(c % T for c in fb[1:])
+    run = sc.sst_run(n)
+    got = device_sections(torch_cuda, seb, None, fb, "even", packed=tuple(a.copy() for a in run))  # run is read-only
+    check_sections(got, host_sections_packed(seb, run, fb), "even", f"1026 tiles, {files} files: host half")
+    check_sections(got, sc.sst_cut(run, fb), "even", f"1026 tiles, {files} files: closed form")
 
 
 def test_fixed_stride_layout(seb, torch_cuda):

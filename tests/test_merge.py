@@ -12,6 +12,7 @@ import pytest
 
 import block_ref as br
 import merge_ref as mr
+import scale_ref as sc
 
 
 def host_merge(seb, runs_blocks, flags=0, **kw):
@@ -178,6 +179,73 @@ def test_unsorted_and_equal_neighbours_are_refused(seb):
     assert ei.value.code == -1 and "run 0 entry 2" in str(ei.value)
     got, _ = host_merge(seb, [[br.encode_block([], num=1, pad=True)]], full_blen=True)
     assert got == [(b"", b"", 0)]
+
+
+def test_emit_refuses_sizes_that_are_not_the_plans(seb):
+    pool, blen, rb = mr.pool_of([mr.run_blocks([(b"k%03d" % i, b"val", 0) for i in range(50)])])
+    n_in, n_out, kb, vb, sh, dr = seb.merge_plan(pool, blen, rb)
+    for sizes in ((n_in, n_out - 1, kb, vb, sh, dr), (n_in, n_out, kb - 1, vb, sh, dr), (n_in, n_out, kb, vb - 1, sh, dr),
+                  (n_in, n_out + 1, kb, vb, sh, dr)):
+        with pytest.raises(seb.SebError) as ei:
+            seb.merge_emit(pool, blen, rb, 0, sizes=sizes)
+        assert ei.value.code == -1
+
+
+# ------------------------------------------------------------------ the shapes of test_gpu_merge.py's scale tests
+
+T = 1024
+
+
+def check_arrays(out, want, name):
+    arrays, sizes = want
+    assert out[5] == sizes, (name, out[5], sizes)
+    for j, what in enumerate(("keys", "key_off", "vals", "val_off", "deleted")):
+        assert np.array_equal(out[j], arrays[j]), (name, what)
+
+
+def test_scale_pool_is_the_rule(seb):
+    """scale_ref.merge_pool itself at a size the restatement takes: its blocks decode as loadBlock decodes them,
+    and its closed form is rule_merge's answer; an empty run among them."""
+    for total, nruns, space in ((3000, 7, 2000), (40, 9, 30), (5, 8, 100)):
+        pool, blen, rb, want = sc.merge_pool(total, nruns, space)
+        runs = [[bytes(pool[b * 4096:b * 4096 + int(blen[b])]) for b in range(rb[r], rb[r + 1])] for r in range(nruns)]
+        ents = mr.decoded(runs)
+        assert all(len(mr.load_block(img)) == (len(img) - 4) // 21 <= sc.PER_BLOCK for run in runs for img in run)
+        for flags in (0, 1):
+            arrays, sizes = want[flags]
+            assert mr.unpack(*arrays) == mr.as_bytes(mr.rule_merge(ents, bool(flags)))
+            assert sizes[0] == sum(len(e) for e in ents) == sizes[1] + sizes[4] + sizes[5]
+            check_arrays(seb.merge_emit(pool, blen, rb, flags), want[flags], f"{nruns} runs")
+
+
+@pytest.mark.parametrize("total,nruns,space", [(140 * T, 17, 400_000), (1024 * T + 40_000, 5, 3_000_000), (12_000, 1025, 100_000)])
+def test_scale_pools_equal_the_closed_form(seb, total, nruns, space):
+    pool, blen, rb, want = sc.merge_pool(total, nruns, space)
+    for flags in (0, seb.MERGE_DROP_TOMBSTONES):
+        arrays, sizes = want[flags]
+        assert total * 0.9 < sizes[0] <= total and sizes[4] > 0 and (sizes[5] > 0) == bool(flags)
+        assert seb.merge_plan(pool, blen, rb, flags) == sizes
+        check_arrays(seb.merge_emit(pool, blen, rb, flags), want[flags], f"{nruns} runs, flags {flags}")
+
+
+@pytest.mark.parametrize("nb,bounds", sc.GROUP_POOLS, ids=[f"{nb}-{b[2]}" for nb, b in sc.GROUP_POOLS])
+def test_block_group_pools_follow_the_rule(seb, nb, bounds):
+    runs = sc.group_runs(nb, bounds)
+    ents = mr.decoded(runs)
+    assert sum(len(run) for run in runs) == nb and sum(len(e) for e in ents) == 3 * (nb - sum(b < nb for b in {255, 256, nb - 1}))
+    for flags in (0, seb.MERGE_DROP_TOMBSTONES):
+        got, plan = host_merge(seb, runs, flags, fill=0xCC)
+        assert got == mr.as_bytes(mr.rule_merge(ents, bool(flags))) and plan[4] > 0
+
+
+@pytest.mark.parametrize("nruns", [16, 17, 33, 257, 1025])
+def test_many_runs_follow_the_rule(seb, nruns):
+    blocks = [mr.run_blocks(run) for run in sc.many_runs(nruns)]
+    ents = mr.decoded(blocks)
+    assert sum(not run for run in blocks) >= nruns // 10
+    for flags in (0, seb.MERGE_DROP_TOMBSTONES):
+        got, plan = host_merge(seb, blocks, flags)
+        assert got == mr.as_bytes(mr.rule_merge(ents, bool(flags))) and plan[4] > 0
 
 
 def test_emit_refuses_sizes_that_are_not_the_plans(seb):

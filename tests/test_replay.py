@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import memtable_ref as mref
+import scale_ref as sc
 
 
 def replay(seb, records, image=None, off=None):
@@ -148,3 +149,43 @@ def test_emit_refuses_other_sizes_and_writes_nothing_past_them(seb):
         with pytest.raises(seb.SebError) as ei:
             seb.wal_replay_emit(image, off, sizes=tuple(bad))
         assert ei.value.code == -1 and "plan" in str(ei.value)
+
+
+# ------------------------------------------------------------------ the shapes of test_gpu_replay.py's scale tests
+
+T = 1024
+
+
+def check_arrays(out, want, sizes, name):
+    assert out[6] == sizes, (name, out[6], sizes)
+    for j, what in enumerate(("keys", "key_off", "vals", "val_off", "deleted", "seq")):
+        assert np.array_equal(out[j], want[j]), (name, what)
+
+
+@pytest.mark.parametrize("n,distinct", [(129 * T + 3, 50_000), (1024 * T + 1025, 400_000)])
+def test_scale_logs_equal_the_closed_form(seb, n, distinct):
+    """The host half on scale_ref.replay_log: the reference of the device's many-tile tests, held to numpy's lexsort."""
+    image, off, want, sizes = sc.replay_log(n, distinct)
+    assert sizes[0] == n and distinct // 2 < sizes[1] <= distinct and 0 < sizes[5] < sizes[1]
+    assert seb.wal_replay_plan(image, off) == sizes
+    check_arrays(seb.wal_replay_emit(image, off), want, sizes, f"n={n}")
+
+
+def test_scale_log_is_a_wal_and_last_wins_is_the_memtable(seb):
+    """The generators themselves at a size the literal restatement takes: replay_log's image parses as ReadAll
+    parses it (CRCs included) and replays as recoverFromWAL does; last_wins equals memtable_ref.expected."""
+    image, off, want, sizes = sc.replay_log(3 * T + 5, 700)
+    recs = [(k, v, s, 1 if d else 0) for k, v, s, d in mref.read_all(image.tobytes())]
+    assert len(recs) == 3 * T + 5
+    assert (mref.unpack(*want), sizes) == mref.expected(recs) == sc.last_wins(recs)
+    recs = mref.random_log(np.random.default_rng(5), 2000)
+    assert sc.last_wins(recs) == mref.expected(recs)
+
+
+@pytest.mark.parametrize("distinct", [0, 1], ids=["few_keys", "distinct_keys"])
+@pytest.mark.parametrize("n", [8 * T + 1, 16 * T, 17 * T - 5, 33 * T + 1])
+def test_deep_logs_equal_last_wins(seb, n, distinct):
+    recs, image, off, want, sizes = sc.deep_log(n, distinct)
+    out = seb.wal_replay_emit(image, off)
+    assert out[6] == sizes and mref.unpack(*out[:6]) == want
+    assert (sizes[1] > n // 2) == bool(distinct)

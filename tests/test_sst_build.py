@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import block_ref as br
+import scale_ref as sc
 import sstable_ref as sr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,6 +108,39 @@ def test_random_runs(seb):
             items.insert(at, (b"over%d" % r, bytes(rng.integers(0, 256, int(rng.integers(4080, 9000)), dtype=np.uint8)), 0))
         blocks += check_against_ref(seb, f"random{r}", items, key_pad=r % 4, val_pad=r % 3)[0]
     assert blocks > 1000
+
+
+def test_scale_run_is_the_builder(seb):
+    """scale_ref.sst_run / sst_cut themselves at a size the restatement takes: the closed form equals
+    sstable_ref.sections file by file, an empty file and a one-entry file among them."""
+    n = 1000
+    run = sc.sst_run(n)
+    kd, koff, vd, voff, dl = run
+    items = [(kd[8 * i:8 * i + 8].tobytes(), vd[4 * i:4 * i + 4].tobytes(), int(dl[i])) for i in range(n)]
+    fb = [0, 0, 1, 195, 389, 777, n]
+    sizes, data, blens, index, meta = sc.sst_cut(run, fb)
+    want = [sr.sections(items[lo:hi]) for lo, hi in zip(fb[:-1], fb[1:])]
+    assert sizes == [(len(w[3]), len(w[0]), len(w[1]), len(w[2]), w[4]) for w in want]
+    assert data == b"".join(w[0] for w in want) and index == b"".join(w[1] for w in want)
+    assert meta == b"".join(w[2] for w in want) and blens == [b for w in want for b in w[3]]
+    assert {int(d) for d in dl} == {0, 1, 2, 255}
+
+
+def test_scale_run_equals_the_closed_form(seb):
+    """The host half on the run of test_gpu_sst_build.py's scan-carry test, as one file and as three."""
+    T = seb.SST_TILE
+    n = 1024 * T + 1025
+    run = sc.sst_run(n)
+    for fb in ([0, n], [0, 300 * T + 77, 301 * T - 5, n]):
+        sizes, data, blens, index, meta = sc.sst_cut(run, fb)
+        at = [0, 0, 0]
+        for f, (lo, hi) in enumerate(zip(fb[:-1], fb[1:])):
+            kd, koff, vd, voff, dl = sc.sst_slice(run, lo, hi)
+            assert seb.sst_plan((kd, koff), voff) == sizes[f]
+            d, x, m = seb.sst_encode((kd, koff), vd, voff, dl)
+            assert d == data[at[0]:at[0] + len(d)] and x == index[at[1]:at[1] + len(x)] and m == meta[at[2]:at[2] + len(m)]
+            at = [at[0] + len(d), at[1] + len(x), at[2] + len(m)]
+        assert at == [len(data), len(index), len(meta)] and sum(s[0] for s in sizes) == len(blens)
 
 
 def test_capacity_one_byte_short(seb):
