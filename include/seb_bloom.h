@@ -658,6 +658,89 @@ int seb_wal_recover(seb_ctx *ctx, const uint8_t *image, uint64_t bytes, uint8_t 
                     uint64_t *key_off, uint8_t *vals, uint64_t val_cap, uint64_t *val_off, uint8_t *deleted,
                     uint64_t *seq, uint64_t entry_cap, seb_replay_sizes *sizes);
 
+/* ------------- batched memtable lookup: LSM.Get's first two steps, and the join with the SSTables' answer ---- */
+/* Before it looks at any file, LSM.Get asks the active memtable and then the immutable one (lsm/lsm.go:144-166),
+ * and whichever holds the key ends the Get.  MemTable.Get (lsm/memtable.go:95-112) is
+ *   idx := sort.Search(len(entries), entries[i].Key >= key);  idx < len && entries[idx].Key == key
+ * over the sorted slice that GetAllEntries() returns (memtable.go:129-137): a sorted run in the builder's input
+ * layout, keys / key_off / vals / val_off / deleted / seq, exactly what seb_dev_wal_replay_emit and
+ * seb_dev_merge_emit write.  This group looks a key batch up in up to SEB_MEM_MAX_RUNS such runs.
+ *
+ * Semantics, bit-exact with the reference:
+ *   - runs are visited in array order: run 0 is the active memtable, run 1 the immutable one.
+ *   - the first run that holds the key decides: SEB_MEM_FOUND, or SEB_MEM_TOMBSTONE where deleted[e] != 0 (ANY
+ *     non-zero byte, the builder's input rule).  Later runs are not consulted: a tombstone in run 0 hides a
+ *     value in run 1.  A key held by no run: SEB_MEM_NONE.
+ *   - A TOMBSTONE IN A MEMTABLE ENDS LSM.Get with "not found" and no SSTable is read (lsm.go:150-153,160-163),
+ *     unlike a tombstone inside an SSTable, which falls through to older files (seb_dev_resolve_rows).  So the
+ *     memtable step has a status of its own, and seb_dev_get_join makes LSM.Get's decision over both halves.
+ *   - order is Go string order: bytewise, a key before its extensions; the empty key is a key like any other.
+ * Outputs per key (status required, the others nullable): status u8; run u8 = the deciding run, 0xFF for none;
+ * entry u32 = the deciding entry, SEB_MEM_NO_ENTRY for none; vloc u64 = val_off[e] and vlen u32 = val_off[e+1] -
+ * val_off[e], both 0 unless the status is SEB_MEM_FOUND (Delete stores Value nil: a tombstone reports no value);
+ * seq u64 = the entry's sequence, 0 for none and where the deciding run has no seq array.
+ *
+ * The one stated refusal: a run whose keys do not increase STRICTLY is SEB_ERR_INVALID.  sort.Search on an
+ * unsorted slice answers by its probe sequence, and no memtable produces one (Put and Delete keep one entry
+ * per key in order); the block locator refuses unsorted indexes for the same reason.  Also refused: key_off
+ * that decreases or passes key_bytes, val_off that decreases, a key or a value of 2^32 bytes or more.  The
+ * checks run entry by entry (an entry's key offsets, its value offsets, then its key against its
+ * predecessor's) and seb_last_error names the first entry that fails ("entry E").  Limits: n < 2^32 entries
+ * per run, keys->n < 2^32. */
+#define SEB_MEM_MAX_RUNS 8u
+enum seb_mem_status { SEB_MEM_NONE = 0, SEB_MEM_FOUND = 1, SEB_MEM_TOMBSTONE = 2 };
+#define SEB_MEM_NO_ENTRY UINT32_MAX
+typedef struct seb_run {            /* a sorted run in the builder's input layout */
+    const uint8_t *keys;  uint64_t key_bytes;   /* bytes addressable from keys */
+    const uint64_t *key_off;                    /* n + 1, key_off[0] may be != 0 */
+    const uint64_t *val_off;                    /* n + 1, val_off[0] may be != 0 */
+    const uint8_t *deleted;                     /* n; any non-zero byte = deleted (the builder's rule); NULL: none */
+    const uint64_t *seq;                        /* n; nullable */
+    uint64_t n;                                 /* < 2^32 */
+} seb_run;
+
+/* Host only: the run pointers and the keys are host memory.  Every run is checked first, as seb_dev_run_index
+ * checks it (SEB_ERR_INVALID, "run R: entry E"); then every key is looked up.  num_runs == 0, or runs of 0
+ * entries: everything is SEB_MEM_NONE.  num_runs > SEB_MEM_MAX_RUNS or a null required pointer:
+ * SEB_ERR_INVALID.  It is the reference for the device form and what a caller without a GPU uses. */
+int seb_runs_search(const seb_keys *keys, const seb_run *runs, uint32_t num_runs, uint8_t *status, uint8_t *run,
+                    uint32_t *entry, uint64_t *vloc, uint32_t *vlen, uint64_t *seq);
+/* Host only: seb_dev_get_join on host arrays. */
+int seb_get_join(const uint8_t *mem_status, const uint8_t *sst_status, uint64_t n, uint8_t *status, uint8_t *source);
+
+/* A run's device index: opaque device memory of seb_dev_run_index_size(n) bytes (0 for n == 0 and for
+ * n >= 2^32), 16-byte aligned; it holds the zero-padded big-endian 16-byte prefix of every key (two u64 per
+ * entry, the layout seb_registry_put_index uses) behind a 16-byte header.  seb_dev_run_index (`run`: a HOST
+ * struct of device pointers, key_off / val_off / seq 8-byte aligned, keys and deleted at any byte alignment)
+ * builds it and runs the checks above on the device; it SYNCHRONISES and returns SEB_ERR_INVALID naming the
+ * first offending entry, SEB_OK otherwise.  No key byte of an entry is read before its offsets and its
+ * predecessor's have passed.  n == 0 is valid: nothing is launched and index may be null.  A run that changes
+ * needs its index built again. */
+uint64_t seb_dev_run_index_size(uint64_t n);
+int seb_dev_run_index(const seb_run *run, void *index, uint64_t index_bytes, void *stream);
+/* Device pointers, not synchronised; `runs` and `index` are HOST arrays of num_runs elements (index[r] may be
+ * null where runs[r].n == 0).  Keys in every seb_keys layout at any byte alignment.  num_runs == 0, or runs of
+ * 0 entries: everything is SEB_MEM_NONE.  num_runs > SEB_MEM_MAX_RUNS, a null required pointer or
+ * keys->n >= 2^32: SEB_ERR_INVALID.  keys->n == 0: nothing is launched.  Nothing outside the n elements of each
+ * output is written.  On any index content nothing is read outside the runs' arrays as seb_dev_run_index
+ * checked them and the first seb_dev_run_index_size(n) bytes of each index: a stale index gives wrong answers,
+ * never an out-of-bounds read. */
+int seb_dev_runs_search(const seb_keys *keys, const seb_run *runs, const void *const *index, uint32_t num_runs,
+                        uint8_t *status, uint8_t *run, uint32_t *entry, uint64_t *vloc, uint32_t *vlen, uint64_t *seq,
+                        void *stream);
+/* LSM.Get's decision over both halves; device pointers, not synchronised.  sst_status is the array
+ * seb_dev_resolve_rows writes.  SEB_MEM_FOUND gives SEB_GET_FOUND; SEB_MEM_TOMBSTONE gives SEB_GET_MISS, also
+ * where sst_status[i] is SEB_GET_ERROR: the reference has returned before it reads any file; SEB_MEM_NONE gives
+ * sst_status[i].  source[i] (nullable) = 0 where the memtables decided, 1 where the SSTables' answer stands.
+ * status may alias sst_status. */
+int seb_dev_get_join(const uint8_t *mem_status, const uint8_t *sst_status, uint64_t n, uint8_t *status,
+                     uint8_t *source, void *stream);
+/* The host-buffer form on a context: keys, the runs' arrays and the six outputs in host memory; H2D of each
+ * run's keys, offsets, deleted bytes and sequences (not its values: the answer is a location), the indexes,
+ * the search, D2H; synchronous.  A run that fails its checks: SEB_ERR_INVALID, "run R: entry E". */
+int seb_memtable_get(seb_ctx *ctx, const seb_keys *keys, const seb_run *runs, uint32_t num_runs, uint8_t *status,
+                     uint8_t *run, uint32_t *entry, uint64_t *vloc, uint32_t *vlen, uint64_t *seq);
+
 /* ---------- hash-index shard routing + WAL record checksums (off the bloom path) ---- */
 /* shard[i] = FNV-1a32(key i) & ((1 << shard_bits) - 1), the reference's getShard
  * (hashindex/shard.go:47-52; 256 shards = shard_bits 8).  hash[i] (nullable) = the full FNV-1a32.

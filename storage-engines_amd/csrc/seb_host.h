@@ -6,8 +6,8 @@
 //   seb_filter.cpp    the Go-API filter handle and its CPU fallback
 //   seb_registry.cpp  the registry, MultiGet, the index walk and the block locator
 //   seb_sstable.cpp   the block-search, SSTable-builder and compaction-merge entry points
-//   seb_recover.cpp   the WAL replay's entry points and seb_wal_recover
-//   seb_memtable.cpp  the host half of the WAL replay (no HIP dependency; seb_memtable.h)
+//   seb_recover.cpp   the WAL replay's entry points and seb_wal_recover; the memtable lookup's and seb_memtable_get
+//   seb_memtable.cpp  the host half of the WAL replay and of the memtable lookup (no HIP dependency; seb_memtable.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -219,6 +219,7 @@ struct seb_ctx {
     seb::DevBuf sst_in, sst_ws, sst_out;  // seb_sst_build: the run, the plan's workspace, the three sections
     seb::DevBuf mrg_in, mrg_ws, mrg_out;  // seb_merge: pool + blen + counts, the plan's workspace, the five output arrays
     seb::DevBuf rpl_in, rpl_ws, rpl_out;  // seb_wal_recover: image + offsets + ok, the plan's workspace, the six output arrays
+    seb::DevBuf mg_runs, mg_out;  // seb_memtable_get: the runs' arrays and indexes, a chunk's six output arrays
     seb::PinBuf hkeys, hbits;  // small filter builds: keys in, bits out, read and written by the kernels
     uint64_t chunk_bytes = 64ull << 20;
     std::vector<uint64_t> off_tmp[2];

@@ -243,6 +243,45 @@ hipError_t launch_replay_emit(const uint8_t *data, const uint64_t *rec_off, cons
                               uint64_t *key_off, uint8_t *vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq,
                               hipStream_t s);
 
+// seb_memget.hip: the batched memtable lookup (lsm/lsm.go:144-166 over lsm/memtable.go:95-112): a key batch
+// against up to kMemRuns sorted runs in the builder's input layout, the first run that holds a key deciding.
+constexpr uint32_t kMemRuns = 8;  // SEB_MEM_MAX_RUNS
+enum : uint32_t { kMemStatusNone = 0, kMemStatusFound = 1, kMemStatusTombstone = 2 };
+struct MemRun {  // device pointers; pre = run_index_prefixes(the run's index)
+    const uint64_t *pre;   // entry e: pre[2e], pre[2e+1] = its key's first 16 bytes, zero padded, big-endian (16-B aligned)
+    const uint64_t *koff;  // n + 1 offsets into bytes
+    const uint64_t *voff;  // n + 1 value offsets
+    const uint8_t *bytes;  // the keys' bytes, read only where 16-byte prefixes tie
+    const uint8_t *deleted;  // nullable
+    const uint64_t *seq;     // nullable
+    uint64_t key_bytes;
+    uint32_t n;
+    uint32_t pad;
+};
+struct MemRunTab {  // passed by value (kernel arguments)
+    MemRun r[kMemRuns];
+    uint32_t nruns;
+    uint32_t pad;
+};
+struct MemOut {  // n elements each; all but status nullable
+    uint8_t *status, *run;
+    uint32_t *entry;
+    uint64_t *vloc;
+    uint32_t *vlen;
+    uint64_t *seq;
+};
+uint64_t run_index_bytes(uint64_t n);  // 0 for n == 0
+const uint64_t *run_index_prefixes(const void *index);
+// n >= 1; the index is 16-byte aligned device memory of run_index_bytes(n).  Synchronises the stream; *err_host =
+// entry << 2 | (0: its key offsets, 1: its value offsets, 2: not above its predecessor) of the least offender,
+// all ones for none.
+hipError_t launch_run_index(const uint8_t *bytes, uint64_t key_bytes, const uint64_t *koff, const uint64_t *voff,
+                            uint32_t n, void *index, uint64_t *err_host, hipStream_t s);
+hipError_t launch_runs_search(const KeyBatch &kb, const MemRunTab &tab, const MemOut &out, hipStream_t s);
+// status may be sst itself; source may be null.
+hipError_t launch_get_join(const uint8_t *mem, const uint8_t *sst, uint64_t n, uint8_t *status, uint8_t *source,
+                           hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

@@ -13,6 +13,9 @@
 //
 // That is a sort by (key, record index) with the last record of each key winning.  One walk serves plan and
 // emit: out == nullptr only sizes.
+//
+// Below it, the host half of the batched memtable lookup over such runs (run_check, runs_search, get_join;
+// tools/sanitize/memget_check.cpp compiles this file alone as well).
 #include "seb_memtable.h"
 
 #include <algorithm>
@@ -115,6 +118,94 @@ int replay_walk(const uint8_t *data, const uint64_t *rec_off, uint64_t n, const 
     } catch (const std::bad_alloc &) {
         return -3;
     }
+}
+
+// ------------------------------------------------ batched memtable lookup (lsm/memtable.go:95-112, lsm/lsm.go:144-166)
+//
+//   MemTable.Get  idx := sort.Search(len(entries), entries[i].Key >= key); idx < len && entries[idx].Key == key
+//                 -> (value, found = !deleted); LSM.Get returns on `found || value == nil && ...`: whichever
+//                 memtable holds the key ends the Get, the active one first (lsm.go:148-166)
+//   a run         GetAllEntries() in the builder's input layout, which the WAL replay and the merge emit
+
+namespace {
+inline int bytes_cmp(const uint8_t *a, uint64_t an, const uint8_t *b, uint64_t bn) {
+    const uint64_t n = an < bn ? an : bn;
+    const int c = n ? memcmp(a, b, n) : 0;
+    return c ? c : an < bn ? -1 : an > bn ? 1 : 0;
+}
+}  // namespace
+
+int run_check(const Run &r, uint64_t *entry) {
+    if (r.n >= (1ull << 32)) return -5;
+    if (r.n && (!r.key_off || !r.val_off || (!r.keys && r.key_bytes))) return -1;
+    for (uint64_t e = 0; e < r.n; ++e) {
+        if (entry) *entry = e;
+        const uint64_t k0 = r.key_off[e], k1 = r.key_off[e + 1];
+        if (k1 < k0 || k1 > r.key_bytes || k1 - k0 >= (1ull << 32)) return -2;
+        const uint64_t v0 = r.val_off[e], v1 = r.val_off[e + 1];
+        if (v1 < v0 || v1 - v0 >= (1ull << 32)) return -3;
+        if (e) {  // entry e - 1 has passed, so its bytes may be read
+            const uint64_t p0 = r.key_off[e - 1];
+            if (bytes_cmp(r.keys + p0, k0 - p0, r.keys + k0, k1 - k0) >= 0) return -4;
+        }
+    }
+    return 0;
+}
+
+int runs_search(const KeysView &kb, const Run *runs, uint32_t num_runs, uint8_t *status, uint8_t *run, uint32_t *entry,
+                uint64_t *vloc, uint32_t *vlen, uint64_t *seq, uint32_t *bad_run, uint64_t *bad_entry) {
+    if (num_runs > kMemMaxRuns || (num_runs && !runs)) return -1;
+    if (kb.n >= (1ull << 32)) return -6;
+    if (kb.n && (!status || (!kb.data && (kb.offsets || kb.stride)))) return -1;
+    for (uint32_t r = 0; r < num_runs; ++r) {
+        if (bad_run) *bad_run = r;
+        const int rc = run_check(runs[r], bad_entry);
+        if (rc) return rc;
+    }
+    for (uint64_t i = 0; i < kb.n; ++i) {
+        const uint64_t o = kb.offsets ? kb.offsets[i] : i * (uint64_t)kb.stride;
+        const uint64_t klen = kb.offsets ? kb.offsets[i + 1] - o : kb.stride;
+        const uint8_t *key = kb.data + o;
+        uint8_t st = kMemNone, rr = 0xFF;
+        uint32_t ee = kMemNoEntry, vn = 0;
+        uint64_t vl = 0, sq = 0;
+        for (uint32_t r = 0; r < num_runs && st == kMemNone; ++r) {
+            const Run &t = runs[r];
+            uint64_t a = 0, b = t.n;  // sort.Search: the least index whose key is >= key
+            while (a < b) {
+                const uint64_t h = (a + b) >> 1;
+                if (bytes_cmp(t.keys + t.key_off[h], t.key_off[h + 1] - t.key_off[h], key, klen) < 0)
+                    a = h + 1;
+                else
+                    b = h;
+            }
+            if (a >= t.n || bytes_cmp(t.keys + t.key_off[a], t.key_off[a + 1] - t.key_off[a], key, klen) != 0) continue;
+            const bool del = t.deleted && t.deleted[a] != 0;
+            st = del ? kMemTombstone : kMemFound;
+            rr = (uint8_t)r;
+            ee = (uint32_t)a;
+            if (!del) vl = t.val_off[a], vn = (uint32_t)(t.val_off[a + 1] - t.val_off[a]);  // Delete stores Value nil
+            sq = t.seq ? t.seq[a] : 0;
+        }
+        status[i] = st;
+        if (run) run[i] = rr;
+        if (entry) entry[i] = ee;
+        if (vloc) vloc[i] = vl;
+        if (vlen) vlen[i] = vn;
+        if (seq) seq[i] = sq;
+    }
+    return 0;
+}
+
+int get_join(const uint8_t *mem_status, const uint8_t *sst_status, uint64_t n, uint8_t *status, uint8_t *source) {
+    if (n && (!mem_status || !sst_status || !status)) return -1;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint8_t m = mem_status[i];
+        const uint8_t s = m == kMemFound ? 1 /* SEB_GET_FOUND */ : m == kMemTombstone ? 0 /* SEB_GET_MISS */ : sst_status[i];
+        if (source) source[i] = m == kMemNone ? 1 : 0;
+        status[i] = s;
+    }
+    return 0;
 }
 
 }  // namespace seb

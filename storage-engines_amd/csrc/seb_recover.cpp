@@ -1,5 +1,6 @@
 // seb_recover.cpp — the WAL replay's entry points: the C ABI over its host half (seb_memtable.cpp) and its
 // kernels (seb_replay.hip), and seb_wal_recover, ReadAll + recoverFromWAL on host buffers through a context.
+// Below them the batched memtable lookup's, over the same host file and seb_memget.hip, and seb_memtable_get.
 #include <new>
 
 #include "seb_host.h"
@@ -190,4 +191,209 @@ extern "C" int seb_wal_recover(seb_ctx *c, const uint8_t *image, uint64_t bytes,
     if (no && seq) HIP_OR_FAIL(hipMemcpyAsync(seq, o + o_seq, 8 * no, hipMemcpyDeviceToHost, s));
     HIP_OR_FAIL(hipStreamSynchronize(s));
     return SEB_OK;
+}
+
+// ------------------------------------------------ batched memtable lookup (lsm/lsm.go:144-166, lsm/memtable.go:95-112)
+
+static_assert(sizeof(seb_run) == sizeof(seb::Run) && sizeof(seb_run) == 56, "seb_run layout");
+static_assert(SEB_MEM_MAX_RUNS == seb::kMemMaxRuns && SEB_MEM_MAX_RUNS == seb::kMemRuns, "SEB_MEM_MAX_RUNS");
+
+// run < 0: the call has one run and does not number it
+static int memget_rc(int rc, int run, uint64_t entry, const char *who) {
+    char where[48] = "";
+    if (run >= 0) snprintf(where, sizeof where, "run %d: ", run);
+    const unsigned long long e = (unsigned long long)entry;
+    switch (rc) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_INVALID, "%s: %sentry %llu: key_off decreases, passes key_bytes or spans 2^32 bytes or more", who,
+                    where, e);
+    case -3:
+        return fail(SEB_ERR_INVALID, "%s: %sentry %llu: val_off decreases or spans 2^32 bytes or more", who, where, e);
+    case -4:
+        return fail(SEB_ERR_INVALID, "%s: %sentry %llu is not above its predecessor (a run's keys increase strictly)", who,
+                    where, e);
+    case -5:
+        return fail(SEB_ERR_INVALID, "%s: %s2^32 entries or more", who, where);
+    case -6:
+        return fail(SEB_ERR_INVALID, "%s: 2^32 keys or more", who);
+    default:
+        return fail(SEB_ERR_INVALID, "%s: a null argument, or more than %u runs", who, SEB_MEM_MAX_RUNS);
+    }
+}
+
+extern "C" int seb_runs_search(const seb_keys *keys, const seb_run *runs, uint32_t num_runs, uint8_t *status, uint8_t *run,
+                               uint32_t *entry, uint64_t *vloc, uint32_t *vlen, uint64_t *seq) {
+    const char *who = "seb_runs_search";
+    int rc;
+    if ((rc = check_keys(keys, who)) || (rc = validate_offsets(keys, who))) return rc;
+    uint32_t bad_run = 0;
+    uint64_t bad_entry = 0;
+    rc = seb::runs_search(seb::KeysView{keys->data, keys->offsets, keys->n, keys->stride}, (const seb::Run *)runs, num_runs,
+                          status, run, entry, vloc, vlen, seq, &bad_run, &bad_entry);
+    return memget_rc(rc, (int)bad_run, bad_entry, who);
+}
+
+extern "C" int seb_get_join(const uint8_t *mem_status, const uint8_t *sst_status, uint64_t n, uint8_t *status,
+                            uint8_t *source) {
+    if (seb::get_join(mem_status, sst_status, n, status, source) != 0)
+        return fail(SEB_ERR_INVALID, "seb_get_join: null argument");
+    return SEB_OK;
+}
+
+extern "C" uint64_t seb_dev_run_index_size(uint64_t n) { return n >= (1ull << 32) ? 0 : run_index_bytes(n); }
+
+static int check_dev_run(const seb_run *r, const char *who) {
+    if (r->n >= (1ull << 32)) return memget_rc(-5, -1, 0, who);
+    if (r->n && (!r->key_off || !r->val_off || (!r->keys && r->key_bytes) || ((uintptr_t)r->key_off & 7) ||
+                 ((uintptr_t)r->val_off & 7) || ((uintptr_t)r->seq & 7)))
+        return fail(SEB_ERR_INVALID, "%s: a run's null key_off, val_off or keys, or offsets or seq that are not 8-byte aligned", who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_run_index(const seb_run *run, void *index, uint64_t index_bytes, void *stream) {
+    const char *who = "seb_dev_run_index";
+    enter();
+    int rc;
+    if (!run) return fail(SEB_ERR_INVALID, "%s: null run", who);
+    if ((rc = check_dev_run(run, who))) return rc;
+    if (run->n == 0) return SEB_OK;
+    if (!index || ((uintptr_t)index & 15)) return fail(SEB_ERR_INVALID, "%s: the index is null or not 16-byte aligned", who);
+    const uint64_t want = run_index_bytes(run->n);
+    if (index_bytes < want)
+        return fail(SEB_ERR_INVALID, "%s: index %llu < %llu bytes for %llu entries", who, (unsigned long long)index_bytes,
+                    (unsigned long long)want, (unsigned long long)run->n);
+    uint64_t err = 0;
+    HIP_OR_FAIL(launch_run_index(run->keys, run->key_bytes, run->key_off, run->val_off, (uint32_t)run->n, index, &err,
+                                 (hipStream_t)stream));
+    if (err != UINT64_MAX) return memget_rc(-2 - (int)(err & 3), -1, err >> 2, who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_runs_search(const seb_keys *keys, const seb_run *runs, const void *const *index, uint32_t num_runs,
+                                   uint8_t *status, uint8_t *run, uint32_t *entry, uint64_t *vloc, uint32_t *vlen,
+                                   uint64_t *seq, void *stream) {
+    const char *who = "seb_dev_runs_search";
+    enter();
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    if (num_runs > SEB_MEM_MAX_RUNS || (num_runs && (!runs || !index))) return memget_rc(-1, -1, 0, who);
+    if (keys->n >= (1ull << 32)) return memget_rc(-6, -1, 0, who);
+    MemRunTab tab{};
+    for (uint32_t r = 0; r < num_runs; ++r) {
+        const seb_run &u = runs[r];
+        if ((rc = check_dev_run(&u, who))) return rc;
+        if (!u.n) continue;
+        if (!index[r] || ((uintptr_t)index[r] & 15))
+            return fail(SEB_ERR_INVALID, "%s: run %u: the index is null or not 16-byte aligned", who, r);
+    }
+    tab.nruns = num_runs;
+    for (uint32_t r = 0; r < num_runs; ++r) {
+        const seb_run &u = runs[r];
+        MemRun &t = tab.r[r];
+        if (!u.n) continue;  // n == 0: the bisection has no step and nothing of the run is read
+        t = MemRun{run_index_prefixes(index[r]), u.key_off, u.val_off, u.keys, u.deleted, u.seq, u.key_bytes, (uint32_t)u.n,
+                   0};
+    }
+    if (keys->n == 0) return SEB_OK;
+    if (!status) return memget_rc(-1, -1, 0, who);
+    HIP_OR_FAIL(launch_runs_search(key_batch(keys), tab, MemOut{status, run, entry, vloc, vlen, seq}, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_get_join(const uint8_t *mem_status, const uint8_t *sst_status, uint64_t n, uint8_t *status,
+                                uint8_t *source, void *stream) {
+    const char *who = "seb_dev_get_join";
+    enter();
+    if (n && (!mem_status || !sst_status || !status)) return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    HIP_OR_FAIL(launch_get_join(mem_status, sst_status, n, status, source, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+// Host buffers through the context: each run's key bytes, offsets, deleted bytes and sequences go up once
+// (its values stay where they are: the answer is a location), its index is built, then a chunk of keys at a
+// time on the compute stream (copy in, search, copy out), as seb_search_blocks does.
+extern "C" int seb_memtable_get(seb_ctx *c, const seb_keys *kb, const seb_run *runs, uint32_t num_runs, uint8_t *status,
+                                uint8_t *run, uint32_t *entry, uint64_t *vloc, uint32_t *vlen, uint64_t *seq) {
+    const char *who = "seb_memtable_get";
+    WsCall ws_call;
+    int rc;
+    if (!c) return fail(SEB_ERR_INVALID, "%s: null ctx", who);
+    if ((rc = check_keys(kb, who)) || (rc = validate_offsets(kb, who))) return rc;
+    if (num_runs > SEB_MEM_MAX_RUNS || (num_runs && !runs) || (kb->n && !status)) return memget_rc(-1, -1, 0, who);
+    if (kb->n >= (1ull << 32)) return memget_rc(-6, -1, 0, who);
+    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
+    uint64_t total = 16;
+    for (uint32_t r = 0; r < num_runs; ++r) {
+        const seb_run &u = runs[r];
+        if (u.n >= (1ull << 32)) return memget_rc(-5, (int)r, 0, who);
+        if (u.n && (!u.key_off || !u.val_off || (!u.keys && u.key_bytes))) return memget_rc(-1, -1, 0, who);
+        if (u.n) total += up(u.key_bytes) + 2 * up(8 * (u.n + 1)) + up(u.n) + up(8 * u.n) + up(run_index_bytes(u.n));
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OR_FAIL(hipSetDevice(c->device));
+    hipStream_t s = c->s_comp;
+    if ((rc = c->mg_runs.reserve(total))) return rc;
+    // the caller's arrays are read by asynchronous copies: whichever way this frame is left, they are waited for
+    struct Drain {
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{s};
+    seb_run drun[SEB_MEM_MAX_RUNS] = {};
+    const void *dindex[SEB_MEM_MAX_RUNS] = {};
+    uint8_t *p = (uint8_t *)c->mg_runs.p;
+    for (uint32_t r = 0; r < num_runs; ++r) {
+        const seb_run &u = runs[r];
+        if (!u.n) continue;
+        seb_run &d = drun[r];
+        auto put = [&](const void *src, uint64_t bytes) -> const uint8_t * {  // null in, null out
+            uint8_t *at = p;
+            if (!src) return nullptr;
+            p += up(bytes);
+            return bytes && hipMemcpyAsync(at, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess ? nullptr : at;
+        };
+        d.n = u.n;
+        d.key_bytes = u.key_bytes;
+        d.keys = u.key_bytes ? put(u.keys, u.key_bytes) : nullptr;
+        d.key_off = (const uint64_t *)put(u.key_off, 8 * (u.n + 1));
+        d.val_off = (const uint64_t *)put(u.val_off, 8 * (u.n + 1));
+        d.deleted = put(u.deleted, u.n);
+        d.seq = (const uint64_t *)put(u.seq, 8 * u.n);
+        if ((u.key_bytes && !d.keys) || !d.key_off || !d.val_off || (u.deleted && !d.deleted) || (u.seq && !d.seq)) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s);
+            return fail(SEB_ERR_INTERNAL, "%s: run %u: a copy to the device failed", who, r);
+        }
+        dindex[r] = p;
+        p += up(run_index_bytes(u.n));
+        if ((rc = seb_dev_run_index(&d, (void *)dindex[r], run_index_bytes(u.n), s))) {
+            if (rc == SEB_ERR_INVALID) {  // the same words with the run's number
+                const std::string msg = last_error();
+                const size_t at = msg.find(": ");
+                return fail(rc, "%s: run %u: %s", who, r, at == std::string::npos ? msg.c_str() : msg.c_str() + at + 2);
+            }
+            return rc;
+        }
+    }
+    if (kb->n == 0) return SEB_OK;
+    return chunks_serial(c, kb, [&](const KeyBatch &dk, const Chunk &ch) -> int {
+        const uint64_t n = dk.n;
+        // per key: vloc u64, seq u64, entry u32, vlen u32, status u8, run u8, each array 16-B aligned
+        const uint64_t o_seq = up(8 * n), o_ent = o_seq + up(8 * n), o_vlen = o_ent + up(4 * n), o_st = o_vlen + up(4 * n),
+                       o_run = o_st + up(n);
+        if ((rc = c->mg_out.reserve(o_run + up(n)))) return rc;
+        uint8_t *o = (uint8_t *)c->mg_out.p;
+        const seb_keys dkeys{dk.data, dk.offsets, dk.n, dk.stride, 0};
+        if ((rc = seb_dev_runs_search(&dkeys, drun, dindex, num_runs, o + o_st, o + o_run, (uint32_t *)(o + o_ent),
+                                      (uint64_t *)o, (uint32_t *)(o + o_vlen), (uint64_t *)(o + o_seq), s)))
+            return rc;
+        HIP_OR_FAIL(hipMemcpyAsync(status + ch.i0, o + o_st, n, hipMemcpyDeviceToHost, s));
+        if (run) HIP_OR_FAIL(hipMemcpyAsync(run + ch.i0, o + o_run, n, hipMemcpyDeviceToHost, s));
+        if (entry) HIP_OR_FAIL(hipMemcpyAsync(entry + ch.i0, o + o_ent, 4 * n, hipMemcpyDeviceToHost, s));
+        if (vloc) HIP_OR_FAIL(hipMemcpyAsync(vloc + ch.i0, o, 8 * n, hipMemcpyDeviceToHost, s));
+        if (vlen) HIP_OR_FAIL(hipMemcpyAsync(vlen + ch.i0, o + o_vlen, 4 * n, hipMemcpyDeviceToHost, s));
+        if (seq) HIP_OR_FAIL(hipMemcpyAsync(seq + ch.i0, o + o_seq, 8 * n, hipMemcpyDeviceToHost, s));
+        return SEB_OK;
+    });
 }

@@ -70,6 +70,12 @@ class seb_replay_sizes(C.Structure):
                 self.max_sequence, self.memtable_size)
 
 
+class seb_run(C.Structure):
+    """A sorted run in the builder's input layout (the memtable lookup): host or device pointers per entry point."""
+    _fields_ = [("keys", C.c_void_p), ("key_bytes", C.c_uint64), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
+                ("deleted", C.c_void_p), ("seq", C.c_void_p), ("n", C.c_uint64)]
+
+
 class seb_filter_ref(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("num_bits", C.c_uint64), ("num_hashes", C.c_uint32),
                 ("reserved", C.c_uint32)]
@@ -171,6 +177,14 @@ _SIGS = {
     "seb_dev_wal_replay_emit": (_i, [_vp, _vp, C.POINTER(seb_replay_sizes), _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_wal_recover": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64,
                              C.POINTER(seb_replay_sizes)]),
+    "seb_runs_search": (_i, [C.POINTER(seb_keys), C.POINTER(seb_run), _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_get_join": (_i, [_vp, _vp, _u64, _vp, _vp]),
+    "seb_dev_run_index_size": (_u64, [_u64]),
+    "seb_dev_run_index": (_i, [C.POINTER(seb_run), _vp, _u64, _vp]),
+    "seb_dev_runs_search": (_i, [C.POINTER(seb_keys), C.POINTER(seb_run), C.POINTER(_vp), _u32, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp]),
+    "seb_dev_get_join": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "seb_memtable_get": (_i, [_vp, C.POINTER(seb_keys), C.POINTER(seb_run), _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_workspace_bytes": (_u64, []),
     "seb_dev_or_slices": (_i, [_vp, _u32, _u64, _vp, _vp]),
     "seb_workspace_release": (_i, []),
@@ -198,6 +212,9 @@ BLOCK_BYTES = 4096    # SEB_BLOCK_BYTES: a block pool slot (readBlock returns at
 NO_BLOCK_ID = 2**32 - 1  # SEB_NO_BLOCK_ID: a cell without a block to search
 CELL_NONE, CELL_MISS, CELL_FOUND, CELL_TOMBSTONE, CELL_TRUNC = range(5)
 GET_MISS, GET_FOUND, GET_ERROR = range(3)
+MEM_NONE, MEM_FOUND, MEM_TOMBSTONE = range(3)  # seb_mem_status
+MEM_MAX_RUNS = 8           # SEB_MEM_MAX_RUNS
+MEM_NO_ENTRY = 2**32 - 1   # SEB_MEM_NO_ENTRY
 
 
 def build_library() -> str:
@@ -443,6 +460,15 @@ class Ctx:
                 err.sizes = sz.as_tuple()
                 raise err
             return _replay_trim(out, sz)
+
+    def memtable_get(self, keys, runs):
+        """LSM.Get's memtable steps from host memory: `runs` are host_run()s, the active memtable first.
+        Returns (status u8, run u8, entry u32, vloc u64, vlen u32, seq u64) per key."""
+        kb = as_keys(keys)
+        arr = _run_array(runs)
+        out = _memget_out(kb.n)
+        check(lib().seb_memtable_get(self._p, kb.ref, arr, len(runs), *[o.ctypes.data for o in out]))
+        return tuple(o[: kb.n] for o in out)
 
     def probe_multi(self, keys, filters: list[tuple[np.ndarray, int, int]]) -> np.ndarray:
         kb = as_keys(keys)
@@ -1246,6 +1272,127 @@ def wal_recover(image, caps=None, device: int = 0):
     ctx = Ctx(device)
     try:
         return ctx.wal_recover(image, caps)
+    finally:
+        ctx.close()
+
+
+# ------------------------------- batched memtable lookup (lsm/lsm.go:144-166 over lsm/memtable.go:95-112)
+
+def host_run(keys, key_off, val_off, deleted=None, seq=None) -> seb_run:
+    """seb_run over host arrays (numpy; keys may be bytes): n = len(key_off) - 1, key_bytes = len(keys).  No
+    array is copied unless its dtype or layout has to change; the struct keeps them alive."""
+    kb = _wal_image_arg(keys)
+    ko = np.ascontiguousarray(key_off, dtype=np.uint64)
+    vo = np.ascontiguousarray(val_off, dtype=np.uint64)
+    if ko.size != vo.size:
+        raise ValueError("key_off and val_off must hold n + 1 offsets each")
+    n = max(ko.size - 1, 0)
+    de = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+    sq = None if seq is None else np.ascontiguousarray(seq, dtype=np.uint64)
+    for name, a in (("deleted", de), ("seq", sq)):
+        if a is not None and a.size < n:
+            raise ValueError(f"{name} holds {a.size} entries, the run has {n}")
+    r = seb_run(kb.ctypes.data if kb.size else None, kb.size, ko.ctypes.data if ko.size else None,
+                vo.ctypes.data if vo.size else None, de.ctypes.data if de is not None and n else None,
+                sq.ctypes.data if sq is not None and n else None, n)
+    r._keep = (kb, ko, vo, de, sq)
+    return r
+
+
+def dev_run(keys, key_off, val_off, deleted=None, seq=None, n: int | None = None, key_bytes: int | None = None) -> seb_run:
+    """seb_run over device tensors (u8 keys and deleted at any alignment; 64-bit key_off, val_off and seq); n
+    defaults to key_off.numel() - 1 and key_bytes to the bytes `keys` holds.  The struct keeps the tensors alive."""
+    nn = (key_off.numel() - 1 if key_off is not None else 0) if n is None else n
+    for name, t, size in (("key_off", key_off, 8 * (nn + 1)), ("val_off", val_off, 8 * (nn + 1)), ("deleted", deleted, nn),
+                          ("seq", seq, 8 * nn)):
+        if nn and t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {nn} entries need {size}")
+    kbytes = (_nbytes(keys) if keys is not None else 0) if key_bytes is None else key_bytes
+    r = seb_run(_ptr(keys), kbytes, _ptr(key_off), _ptr(val_off), _ptr(deleted), _ptr(seq), nn)
+    r._keep = (keys, key_off, val_off, deleted, seq)
+    return r
+
+
+def _run_array(runs):
+    arr = (seb_run * max(len(runs), 1))(*runs)
+    arr._keep = list(runs)
+    return arr
+
+
+def _memget_out(n: int):
+    n1 = max(n, 1)
+    return (np.zeros(n1, np.uint8), np.zeros(n1, np.uint8), np.zeros(n1, np.uint32), np.zeros(n1, np.uint64),
+            np.zeros(n1, np.uint32), np.zeros(n1, np.uint64))
+
+
+def runs_search(keys, runs):
+    """The host half: MemTable.Get of every key over `runs` (host_run()s, the active memtable first), the first
+    run that holds the key deciding.  Returns (status u8, run u8, entry u32, vloc u64, vlen u32, seq u64).  A
+    run that fails its checks: SebError (INVALID) naming "run R: entry E"."""
+    kb = as_keys(keys)
+    arr = _run_array(runs)
+    out = _memget_out(kb.n)
+    check(lib().seb_runs_search(kb.ref, arr, len(runs), *[o.ctypes.data for o in out]))
+    return tuple(o[: kb.n] for o in out)
+
+
+def get_join(mem_status, sst_status):
+    """The host half of LSM.Get's decision over both halves: (status u8, source u8)."""
+    mem = np.ascontiguousarray(mem_status, dtype=np.uint8)
+    sst = np.ascontiguousarray(sst_status, dtype=np.uint8)
+    if mem.shape != sst.shape:
+        raise ValueError("mem_status and sst_status must have one shape")
+    st, src = np.zeros(max(mem.size, 1), np.uint8), np.zeros(max(mem.size, 1), np.uint8)
+    check(lib().seb_get_join(mem.ctypes.data, sst.ctypes.data, mem.size, st.ctypes.data, src.ctypes.data))
+    return st[: mem.size], src[: mem.size]
+
+
+def dev_run_index_size(n: int) -> int:
+    return lib().seb_dev_run_index_size(n)
+
+
+def dev_run_index(run: seb_run, index, index_bytes: int | None = None, stream=None) -> None:
+    """Device form: checks the run (a dev_run()) and builds its index into the tensor `index`
+    (dev_run_index_size(run.n) bytes, 16-byte aligned).  Synchronises; a run that fails: SebError (INVALID)
+    naming "entry E"."""
+    check(lib().seb_dev_run_index(C.byref(run), _ptr(index), (_nbytes(index) if index is not None else 0)
+                                  if index_bytes is None else index_bytes, _stream(stream)))
+
+
+def dev_runs_search(keys: seb_keys, runs, indexes, status, run=None, entry=None, vloc=None, vlen=None, seq=None,
+                    stream=None) -> None:
+    """Device form: `runs` are dev_run()s and `indexes` their index tensors (None for an empty run); status (n
+    u8) and optionally run (n u8), entry (n u32), vloc (n u64), vlen (n u32), seq (n u64).  Not synchronised."""
+    if len(runs) != len(indexes):
+        raise ValueError("one index per run")
+    n = keys.n
+    for name, t, size in (("status", status, n), ("run", run, n), ("entry", entry, 4 * n), ("vloc", vloc, 8 * n),
+                          ("vlen", vlen, 4 * n), ("seq", seq, 8 * n)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {n} keys need {size}")
+    for r, ix in zip(runs, indexes):
+        if r.n and ix is not None and _nbytes(ix) < dev_run_index_size(r.n):
+            raise ValueError(f"an index holds {_nbytes(ix)} bytes, {r.n} entries need {dev_run_index_size(r.n)}")
+    ix = (_vp * max(len(runs), 1))(*[_ptr(t) for t in indexes])
+    check(lib().seb_dev_runs_search(C.byref(keys), _run_array(runs), ix, len(runs), _ptr(status), _ptr(run), _ptr(entry),
+                                    _ptr(vloc), _ptr(vlen), _ptr(seq), _stream(stream)))
+
+
+def dev_get_join(mem_status, sst_status, n: int, status, source=None, stream=None) -> None:
+    """Device form of LSM.Get's decision over the memtables' status and the SSTables' (dev_resolve_rows'):
+    status (n u8, may be sst_status itself) and optionally source (n u8: 0 memtables, 1 SSTables).  Not
+    synchronised."""
+    for name, t in (("mem_status", mem_status), ("sst_status", sst_status), ("status", status), ("source", source)):
+        if t is not None and _nbytes(t) < n:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {n} keys need {n}")
+    check(lib().seb_dev_get_join(_ptr(mem_status), _ptr(sst_status), n, _ptr(status), _ptr(source), _stream(stream)))
+
+
+def memtable_get(keys, runs, device: int = 0):
+    """Ctx.memtable_get on a context made for the call."""
+    ctx = Ctx(device)
+    try:
+        return ctx.memtable_get(keys, runs)
     finally:
         ctx.close()
 
