@@ -8,7 +8,10 @@
 //   k_bkt_scatter  one workgroup per super-tile of keys: hash a round of keys, counting-sort its
 //                  positions by bucket in LDS, append each bucket's run (u16 in-bucket bit index)
 //                  to the fixed-capacity region (bucket, tile); the run lengths go to counts
-//   k_bkt_apply    one workgroup per bucket: stream its ntiles regions, ds_or into an 8 KiB LDS
+//   k_bkt_scatter_bins  the same through fixed LDS bins (k == 7, 512..2275 buckets): whole 16-B
+//                  chunks leave each round, a bucket's partial chunk is carried into the next
+//   k_bkt_apply    one workgroup per bucket: stream the written chunks of its ntiles regions (a
+//                  flat walk over the prefix of their chunk counts), ds_or into an 8 KiB LDS
 //                  image, then OR the image into the filter words the workgroup owns, or for a
 //                  fresh build write them whole (no clear beforehand)
 //
@@ -238,10 +241,15 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter(Src src, uint64_t n, Mo
 // software-pipelines its keys: it hashes key r and issues its 7 claims, then writes key r-1's
 // bins, whose claims returned while key r hashed.  The LDS atomics run under the hashing.
 // After one barrier each bucket's run goes out as 16-B chunks, its S/8 chunks on adjacent lanes
-// of one wave; the run is padded to a multiple of 8 with copies of its last chunk's first index
-// (apply ORs that bit again), so every region offset stays 16-B aligned and apply needs no
-// per-index bounds.  A claim past the bin (a Poisson tail: ~3e-5 of the bucket-
-// rounds with S = 48) is stored straight to its region slot, which the round's start fixes.  The
+// of one wave.  Only whole chunks leave in a round that is not the tile's last: the partial chunk
+// moves to the front of the bin and the next round's claims start behind it, so the padding is
+// paid once per (bucket, tile), not once per round (143 MB of runs at C2 instead of 160 for 140
+// of indices).  The tile's last round pads its run to a multiple of 8 with copies of its last
+// chunk's first index (apply ORs that bit again), so every region offset stays 16-B aligned and
+// apply needs no per-index bounds.  A claim past the bin (a Poisson tail: with up to 7 carried
+// entries ~2.2e-4 of the bucket-rounds with S = 48, 8.6e-6 without them, so the rare path below
+// runs in ~0.9% of the wave-steps) is stored straight to its region slot, which the round's start
+// fixes; such a run sends out its S/8 chunks, pads its tail in the region and carries nothing.  The
 // lane that advances a bucket's fill sits in the wave whose lanes read it, so a round has two
 // barriers.  LDS: bins[nb][S] u16 | cnt[nb] (this round's claims) | fill[nb] (region fill) | a
 // scratch word; two arrays, not one of pairs, so the claim atomics spread over all the banks.
@@ -388,9 +396,50 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter_bins(Src src, uint64_t 
         // write-out: a bucket's S/8 chunks on S/8 adjacent lanes of one wave (64/(S/8) buckets per
         // wave; with S = 48, lanes 60-63 idle), so the lane that advances the bucket's fill runs in
         // the wave whose other lanes read it
-        {
-            constexpr uint32_t NCH = S / 8, BPW = 64 / NCH, NW = THREADS / 64;
-            const uint32_t lane = threadIdx.x & 63u, g = lane / NCH, j = lane - g * NCH;
+        constexpr uint32_t NCH = S / 8, BPW = 64 / NCH, NW = THREADS / 64;
+        const uint32_t lane = threadIdx.x & 63u, g = lane / NCH, j = lane - g * NCH;
+        if (k1 < t1) {
+            // not the tile's last round: only the full chunks leave.  The lane holding the partial
+            // chunk copies it to the front of the bin, the count restarts at c % 8, and the next
+            // round's claims line up behind the carried entries (bin slot sl is still region slot
+            // fill + sl).  No padding, so no pad selects.  The copy follows the group's chunk reads
+            // in program order, and a bucket's lanes sit in one wave, whose LDS operations keep
+            // that order; the fence keeps the compiler from moving the reads below it.
+            for (uint32_t b0 = (threadIdx.x >> 6) * BPW; b0 < nb; b0 += NW * BPW) {
+                const uint32_t b = b0 + g;
+                if (g >= BPW || b >= nb) continue;
+                const uint32_t c = cnt[b], f = fill[b];
+                const uint32_t rb = (b * ntiles + t) * cap;
+                uint4 w = make_uint4(0u, 0u, 0u, 0u);
+                if (j * 8 < c) w = *(const uint4 *)(bins + b * S + j * 8);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                if (j * 8 + 8 <= c) {  // a full chunk (every chunk of a run past its bin is one)
+                    const uint32_t e = f + j * 8;
+                    if (e < cap) {
+                        *(uint4 *)(regions + rb + e) = w;
+                    } else {
+                        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                        for (uint32_t i = 0; i < 8; ++i) bins_overflow_or(ovw, b, (ww[i >> 1] >> ((i & 1) * 16)) & 0xffffu);
+                    }
+                } else if (j * 8 < c && j != 0) {  // the partial chunk (c < S): carried
+                    *(uint4 *)(bins + b * S) = w;
+                }
+                if (j == 0) {
+                    if (c > S) {  // a run past its bin: pad its tail in the region, carry nothing
+                        const uint32_t padded = (c + (PAD - 1)) & ~(PAD - 1);
+                        const uint16_t d = (uint16_t)(w.x & 0xffffu);
+                        for (uint32_t e = f + c; e < f + padded; ++e)
+                            if (e < cap) regions[(uint64_t)rb + e] = d;
+                        cnt[b] = 0u;
+                        fill[b] = f + padded;
+                    } else {
+                        cnt[b] = c & (PAD - 1);
+                        fill[b] = f + (c & ~(PAD - 1));
+                    }
+                }
+            }
+        } else {  // the tile's last (or only) round: everything leaves, padded to whole chunks
             for (uint32_t b0 = (threadIdx.x >> 6) * BPW; b0 < nb; b0 += NW * BPW) {
                 const uint32_t b = b0 + g;
                 if (g >= BPW || b >= nb) continue;
@@ -437,64 +486,68 @@ __global__ __launch_bounds__(THREADS) void k_bkt_scatter_bins(Src src, uint64_t 
 // k_bkt_scatter_bins, whole 16-B chunks, so a region's count is a multiple of 8 and every index
 // below it is valid (a chunk's padding repeats its first index; skipping it by a compare measured
 // slower than OR-ing it: apply 43.0 vs 41.7 us, tools/diag/apply_or_padding.patch reversed).
+// The walk is flat over the chunks that were written: the exclusive prefix of every tile's
+// ceil(min(count, cap) / 8) is scanned into LDS, thread q takes flat chunk q and finds its tile by a
+// branch-free binary search of that prefix (the U searches of a batch interleaved), so no load is
+// issued for a chunk at or past its region's count and no index needs a division.  A thread has
+// U = 4 chunk loads in flight (C2's ~6 chunks per thread as one batch of 8 measured slower, build
+// 0.1512 vs 0.1504 ms: tools/diag/apply_single_batch.patch).
 template <int THREADS, bool FRESH, bool PADDED = false>
 __global__ __launch_bounds__(THREADS) void k_bkt_apply(const uint16_t *__restrict__ regions,
                                                    const uint32_t *__restrict__ counts, uint32_t ntiles, uint32_t cap,
                                                    uint32_t *__restrict__ words, uint64_t nwords,
                                                    uint32_t *__restrict__ ovf) {
+    static_assert(THREADS >= (int)kMaxTiles, "the prefix scan takes one tile per thread");
     __shared__ uint32_t img[kBktWords];
-    __shared__ uint32_t cnt[kMaxTiles];
-    __shared__ uint32_t spilled, longest;
+    __shared__ uint32_t cnt[PADDED ? 1 : kMaxTiles];  // the per-index bound of the unpadded form
+    __shared__ uint32_t pre[THREADS];                  // first flat chunk of tile t; the total past ntiles
+    __shared__ uint32_t wsum[THREADS / 64];
+    __shared__ uint32_t spilled;
     const uint32_t b = blockIdx.x;
+    uint32_t c = 0u;
+    if (threadIdx.x < ntiles) c = counts[(uint64_t)b * ntiles + threadIdx.x];
     for (uint32_t j = threadIdx.x; j < kBktWords; j += blockDim.x) img[j] = 0u;
-    if (threadIdx.x == 0) {
-        spilled = 0u;
-        longest = 0u;
-    }
+    if (threadIdx.x == 0) spilled = 0u;
+    const uint32_t valid = min(c, cap);
+    uint32_t total;  // the scan's barriers also order the zeroing above before what follows
+    pre[threadIdx.x] = block_exclusive_scan((valid + 7) / 8, wsum, &total);
+    if constexpr (!PADDED)
+        if (threadIdx.x < kMaxTiles) cnt[threadIdx.x] = valid;
+    if (c > cap) spilled = 1u;
     __syncthreads();
-    for (uint32_t t = threadIdx.x; t < ntiles; t += blockDim.x) {
-        const uint32_t c = counts[(uint64_t)b * ntiles + t];
-        if (c > cap) spilled = 1u;
-        cnt[t] = min(c, cap);
-        atomicMax(&longest, min(c, cap));
-    }
-    __syncthreads();
-    // walk (tile, chunk) pairs only up to this bucket's longest region, not the capacity (which
-    // keeps 8 sigma of headroom: ~30% fewer iterations at C2)
     const uint32_t stride = cap / 8;  // cap is a multiple of 8: regions are 16-B aligned
-    const uint32_t chunks = (longest + 7) / 8;
-    const uint32_t pairs = ntiles * chunks;
     const uint4 *reg = (const uint4 *)(regions + (uint64_t)b * ntiles * cap);
-    // U chunk loads in flight per thread: they are issued before any count is consulted (every
-    // chunk below the longest region lies inside its region's capacity, so a load past a shorter
-    // region's count is in bounds and is simply not used); checking the count first put one load
-    // per wave in flight at a time
+    // the largest power of two below ntiles: the search's steps reach every tile and stay inside pre[]
+    const uint32_t top = ntiles > 1 ? 1u << (31 - __clz(ntiles - 1)) : 0u;
     constexpr uint32_t U = 4;
-    for (uint32_t q0 = threadIdx.x; q0 < pairs; q0 += U * THREADS) {
+    for (uint32_t q0 = threadIdx.x; q0 < total; q0 += U * THREADS) {
+        uint32_t t[U];  // the last tile whose prefix is <= q: the one that holds flat chunk q
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) t[u] = 0u;
+        for (uint32_t step = top; step; step >>= 1) {
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) t[u] += pre[t[u] + step] <= q0 + u * THREADS ? step : 0u;
+        }
         uint4 v[U];
+        uint32_t ch[U];
 #pragma unroll
         for (uint32_t u = 0; u < U; ++u) {
             const uint32_t q = q0 + u * THREADS;
-            if (q < pairs) {
-                const uint32_t t = q / chunks, c = q - t * chunks;
-                v[u] = reg[t * stride + c];
-            }
+            ch[u] = q - pre[t[u]];
+            if (q < total) v[u] = reg[t[u] * stride + ch[u]];
         }
 #pragma unroll
         for (uint32_t u = 0; u < U; ++u) {
-            const uint32_t q = q0 + u * THREADS;
-            if (q >= pairs) break;
-            const uint32_t t = q / chunks, c = q - t * chunks;
-            const uint32_t valid = cnt[t];
-            if (c * 8 < valid) {
-                const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            if (q0 + u * THREADS >= total) break;
+            uint32_t live = 8;  // PADDED: the padding ORs its chunk's first bit again
+            if constexpr (!PADDED) live = cnt[t[u]] - ch[u] * 8;
+            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
-                for (uint32_t e = 0; e < 8; ++e)
-                    if (PADDED || c * 8 + e < valid) {  // PADDED: the padding ORs its chunk's first bit again
-                        const uint32_t l = (w[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-                        atomicOr(&img[l >> 5], 1u << (l & 31));
-                    }
-            }
+            for (uint32_t e = 0; e < 8; ++e)
+                if (PADDED || e < live) {
+                    const uint32_t l = (w[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
+                    atomicOr(&img[l >> 5], 1u << (l & 31));
+                }
         }
     }
     __syncthreads();
@@ -537,6 +590,21 @@ static uint32_t use_bins(uint64_t m, uint32_t k) { return options().scatter_bins
 
 // One 1024-thread scatter workgroup per CU (two of 512 measured slower).
 constexpr uint32_t kScatterThreads = 1024;
+// apply: 1024 threads per bucket (256 and 512 measured slower)
+constexpr uint32_t kApplyThreads = 1024;
+
+// apply over the plan's regions: FRESH writes every word of the filter, padding included.
+template <bool PADDED>
+static void launch_apply(const BktPlan &p, bool fresh, const uint16_t *regions, const uint32_t *counts, uint32_t *words,
+                         uint64_t m, uint32_t *ovf, hipStream_t s) {
+    auto go = [&](auto kern, uint64_t nwords, uint32_t *o) {
+        hipLaunchKernelGGL(kern, dim3(p.nb), dim3(kApplyThreads), 0, s, regions, counts, p.ntiles, p.cap, words, nwords, o);
+    };
+    if (fresh)
+        go(k_bkt_apply<kApplyThreads, true, PADDED>, (m + 127) / 128 * 4, ovf);
+    else
+        go(k_bkt_apply<kApplyThreads, false, PADDED>, (m + 31) / 32, nullptr);
+}
 // 5 keys per thread per round only while its sort buffer and the two per-bucket arrays fit the
 // 160 KiB of LDS (nb <= 2551, m <= ~167M bits); 4 otherwise.
 static uint32_t scatter_kpt(uint32_t nb) {
@@ -572,7 +640,9 @@ static BktPlan plan_bucketed(uint64_t n, uint64_t m, uint32_t k, uint32_t bins) 
     double c = mu + 8.0 * sqrt(mu > 1 ? mu : 1) + 32.0;
     const double most = rkeys * k;  // never more than every position of the tile
     if (c > most) c = most;
-    if (bins) c += 7.0 * (double)rounds_per_tile;  // each round's run padded to a multiple of 8
+    // (sized for every round's run padded to a multiple of 8; since the rounds carry their partial
+    // chunk only a tile's last run is, but the formula fixes the workspace size and stays)
+    if (bins) c += 7.0 * (double)rounds_per_tile;
     p.cap = ((uint32_t)c + 7) & ~7u;
     auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
     p.off_regions = 0;
@@ -617,7 +687,6 @@ static hipError_t run_bucketed(uint64_t n, const ModArg &md, uint32_t *words, vo
         uint8_t *w = (uint8_t *)ws;
         uint16_t *regions = (uint16_t *)(w + p.off_regions);
         uint32_t *counts = (uint32_t *)(w + p.off_counts);
-        const uint64_t nwords = (md.m + 31) / 32;
         const uint32_t kpt = scatter_kpt(p.nb);
         const size_t lds = ((size_t)kScatterThreads * kpt * 7 + 2 * p.nb + 17) * sizeof(uint32_t);
         hipError_t e = chunk(k0, sn, [&](auto src) -> hipError_t {
@@ -631,12 +700,7 @@ static hipError_t run_bucketed(uint64_t n, const ModArg &md, uint32_t *words, vo
                 if (a != hipSuccess) return a;
                 hipLaunchKernelGGL(scat, dim3(p.ntiles), dim3(kScatterThreads), blds, s, src, sn, md, p.nb, p.tile_keys,
                                    p.round_keys, p.ntiles, p.cap, regions, counts, fresh ? ovf : words);
-                if (fresh)
-                    hipLaunchKernelGGL((k_bkt_apply<1024, true, true>), dim3(p.nb), dim3(1024), 0, s, regions, counts,
-                                       p.ntiles, p.cap, words, (md.m + 127) / 128 * 4, ovf);
-                else
-                    hipLaunchKernelGGL((k_bkt_apply<1024, false, true>), dim3(p.nb), dim3(1024), 0, s, regions, counts,
-                                       p.ntiles, p.cap, words, nwords, nullptr);
+                launch_apply<true>(p, fresh, regions, counts, words, md.m, ovf, s);
                 return hipGetLastError();
             }
             constexpr int K0 = IsPacked<S>::value ? 7 : 0;  // packed sources have no generic-k kernel
@@ -646,13 +710,7 @@ static hipError_t run_bucketed(uint64_t n, const ModArg &md, uint32_t *words, vo
             if (a != hipSuccess) return a;
             hipLaunchKernelGGL(scat, dim3(p.ntiles), dim3(kScatterThreads), lds, s, src, sn, md, p.nb, p.tile_keys,
                                p.ntiles, p.cap, regions, counts, fresh ? ovf : words);
-            // apply: 1024 threads per bucket (256 and 512 measured slower)
-            if (fresh)
-                hipLaunchKernelGGL((k_bkt_apply<1024, true>), dim3(p.nb), dim3(1024), 0, s, regions, counts, p.ntiles,
-                                   p.cap, words, (md.m + 127) / 128 * 4, ovf);
-            else
-                hipLaunchKernelGGL((k_bkt_apply<1024, false>), dim3(p.nb), dim3(1024), 0, s, regions, counts, p.ntiles,
-                                   p.cap, words, nwords, nullptr);
+            launch_apply<false>(p, fresh, regions, counts, words, md.m, ovf, s);
             return hipGetLastError();
         });
         if (e != hipSuccess) return e;
