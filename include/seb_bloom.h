@@ -741,6 +741,136 @@ int seb_dev_get_join(const uint8_t *mem_status, const uint8_t *sst_status, uint6
 int seb_memtable_get(seb_ctx *ctx, const seb_keys *keys, const seb_run *runs, uint32_t num_runs, uint8_t *status,
                      uint8_t *run, uint32_t *entry, uint64_t *vloc, uint32_t *vlen, uint64_t *seq);
 
+/* ------------- memtable write side: Put / Delete batches into WAL records, the memtable's runs and the flush input ---- */
+/* What LSM.Put / LSM.Delete do to the log and to the active memtable (lsm/lsm.go:97-137, 203-235, lsm/wal.go:31-65,
+ * lsm/memtable.go:34-93), for a batch of n ops applied in order by one writer, with lsm.sequence == S before it.
+ *
+ * Sequences: op i gets seq = S + 1 + i (atomic.AddUint64 returns the new value); afterwards lsm.sequence = S + n.
+ * The callers pass first_seq = S + 1.
+ *
+ * The record: WAL.Append(key, value, seq, deleted) writes [crc u32][seq u64][keySize u32][valueSize u32][deleted u8]
+ * [key][value], little-endian, crc = ChecksumIEEE(record[4:]).  LSM.Delete appends value = nil: a Delete op's record
+ * has valueSize = 0 and deleted = 1, WHATEVER VALUE BYTES THE OP ARRAYS CARRY FOR IT; a Put has deleted = 0.  An op is
+ * a Delete where deleted[i] is any non-zero byte (deleted == NULL: none is).  The image of the batch is the
+ * concatenation of its records, rec_off[i+1] - rec_off[i] = 21 + keyLen + (deleted ? 0 : valueLen), rec_off[0] = 0:
+ * what the caller hands to one Write of the log, and what seb_wal_scan / SEB_WAL_VERIFY / seb_wal_replay_* read back.
+ *
+ * The memtable: MemTable.Put / Delete keep one entry per key; a later op of a key replaces the whole entry; tombstones
+ * stay, with a nil value.  So after batches B1..Bk on a memtable that held the run `old`, the memtable equals
+ *   fold([replay(Bk), ..., replay(B1), old])
+ * where replay is the replay group's run of one batch's records and fold keeps, for each distinct key, the entry of
+ * the LOWEST-NUMBERED RUN that holds it (the caller passes the runs newest first, the order seb_dev_runs_search
+ * visits them in).  There is no departure from the reference: (key, run number) is a total order, so every output
+ * byte of the fold is determined.  Tombstones are never dropped: a flush keeps them.
+ *
+ * MemTable.size is path independent: the sum over the entries of keyLen + 16 + valueLen, valueLen 0 for a tombstone.
+ * For a new run put in front of the ACTIVE memtable's runs (the immutable memtable is a separate MemTable and takes
+ * no part) its change is a sum over the new run's entries: an entry whose key no existing run holds adds keyLen + 16
+ * + valueLen; an entry whose key the first existing run that holds it has with value length v_old adds valueLen -
+ * v_old (0 for either length where that entry is a tombstone).
+ *
+ * WHEN TO FREEZE IS THE CALLER'S DECISION.  The reference tests IsFull() after every single op and freezes only when
+ * immutableMemtable == nil, so the size at which a memtable freezes is no invariant of the reference: it runs past
+ * maxSize whenever a flush is pending.  This group reports the size after the batch; the caller decides once per
+ * batch.  There is no per-op cut.  Concurrent writers, file I/O (Write, Sync) and LSM.Scan are out of scope.
+ *
+ * The one refusal of the frame: a key or a value of 2^32 bytes or more (the reference would truncate uint32(len) and
+ * corrupt its log), and offsets that decrease: SEB_ERR_INVALID, and seb_last_error names the lowest offender
+ * ("op I").  The check runs on every op's offsets, a Delete's value offsets included, before any byte of the op is
+ * read.  Limit: n < 2^32.  n == 0 is valid: nothing is launched and the image is empty. */
+typedef struct seb_fold_sizes {
+    uint64_t entries_in, entries_out; /* over all runs / distinct keys */
+    uint64_t key_bytes, val_bytes;    /* of the output run */
+    uint64_t shadowed, tombstones;    /* entries lost to a lower-numbered run / tombstones in the output */
+    uint64_t max_sequence;            /* over ALL input entries, shadowed ones included; 0 where no run has seq */
+    uint64_t memtable_size;           /* MemTable.size of the folded memtable */
+} seb_fold_sizes;
+
+/* Host only.  keys in every seb_keys layout; val_off: n + 1 non-decreasing offsets into vals (val_off[0] may be != 0);
+ * deleted nullable.  seb_wal_frame_plan writes rec_off[0..n] (nullable) and *image_bytes (nullable);
+ * seb_wal_frame_emit writes the sealed image into image[0, image_bytes) (image_bytes not the plan's:
+ * SEB_ERR_INVALID) and nothing outside it.  They are the reference for the device form and what a caller without a
+ * GPU uses. */
+int seb_wal_frame_plan(const seb_keys *keys, const uint64_t *val_off, const uint8_t *deleted, uint64_t *rec_off,
+                       uint64_t *image_bytes);
+int seb_wal_frame_emit(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                       uint64_t first_seq, uint8_t *image, uint64_t image_bytes);
+/* Device pointers (offsets 8-byte aligned; keys, vals, deleted and the image at any byte alignment); image_bytes of
+ * the plan is HOST memory.  seb_dev_wal_frame_plan writes rec_off[0..n] (required), SYNCHRONISES and fills
+ * *image_bytes, so the caller can allocate the image.  seb_dev_wal_frame_emit (not synchronised; rec_off and
+ * image_bytes as the plan left them) writes the sealed image: the records, then SEB_WAL_SEAL's CRCs.  Nothing is
+ * written outside [image, image + image_bytes) or the n + 1 offsets, and nothing is read outside the ops' arrays as
+ * their offsets describe them.  rec_off is trusted as seb_dev_wal_crc trusts it: offsets that are not this batch's
+ * plan are the caller's error. */
+int seb_dev_wal_frame_plan(const seb_keys *keys, const uint64_t *val_off, const uint8_t *deleted, uint64_t *rec_off,
+                           uint64_t *image_bytes, void *stream);
+int seb_dev_wal_frame_emit(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                           uint64_t first_seq, const uint64_t *rec_off, uint8_t *image, uint64_t image_bytes,
+                           void *stream);
+
+/* MemTable.size's change when `fresh` goes in front of the active memtable's `runs` (num_runs <=
+ * SEB_MEM_MAX_RUNS - 1, newest first).  Host: every run and `fresh` are checked as seb_runs_search checks a run
+ * ("run R: entry E"; `fresh` is named "the new run").  Device: `fresh` and `runs` are HOST structs of device
+ * pointers, index[r] is run r's index from seb_dev_run_index (`fresh` needs none); *delta is DEVICE memory (8-byte
+ * aligned) and the call is not synchronised.  num_runs == 0 gives the run's own size.  On any index content nothing
+ * is read outside the runs' arrays as seb_dev_run_index checked them. */
+int seb_run_size_delta(const seb_run *fresh, const seb_run *runs, uint32_t num_runs, int64_t *delta);
+int seb_dev_run_size_delta(const seb_run *fresh, const seb_run *runs, const void *const *index, uint32_t num_runs,
+                           int64_t *delta, void *stream);
+
+/* Fold up to SEB_MEM_MAX_RUNS runs, newest first, into the one run GetAllEntries() hands to the builder.  vals[r] /
+ * val_bytes[r] are run r's value bytes (seb_run carries no value pointer); val_off[n] > val_bytes[r] is
+ * SEB_ERR_INVALID naming "run R".  Output: the builder's input layout exactly as seb_dev_wal_replay_emit writes it:
+ * keys / key_off / vals / val_off (entries_out + 1 offsets each, starting at 0), deleted = 1 or 0, seq (nullable): the
+ * distinct keys in Go string order, the empty key included, each entry from the lowest-numbered run that holds it; a
+ * tombstone comes out with no value, even where its run carries value bytes; seq from the winning entry, 0 where that
+ * run has no seq array.  Limit: fewer than 2^32 entries in total.  num_runs == 0 and runs of 0 entries are valid.
+ *
+ * Host only: every run is checked as seb_runs_search checks it ("run R: entry E").  seb_runs_fold_emit takes `sizes`
+ * as the plan returned them (anything else: SEB_ERR_INVALID). */
+int seb_runs_fold_plan(const seb_run *runs, const uint64_t *val_bytes, uint32_t num_runs, seb_fold_sizes *sizes);
+int seb_runs_fold_emit(const seb_run *runs, const uint8_t *const *vals, const uint64_t *val_bytes, uint32_t num_runs,
+                       uint8_t *keys, uint64_t *key_off, uint8_t *out_vals, uint64_t *val_off, uint8_t *deleted,
+                       uint64_t *seq, const seb_fold_sizes *sizes);
+/* Device: `runs`, `index`, `vals` and `val_bytes` are HOST arrays; the runs' pointers, the indexes (from
+ * seb_dev_run_index, which has refused unsorted runs and bad offsets) and vals[r] are device memory.  The workspace
+ * (seb_dev_runs_fold_workspace_size(total entries) bytes of device memory, 16-byte aligned, opaque; too small:
+ * SEB_ERR_INVALID) carries the plan to the emit and must not be touched in between.  seb_dev_runs_fold_plan
+ * SYNCHRONISES and fills *sizes.  seb_dev_runs_fold_emit (not synchronised; the same runs, indexes and workspace)
+ * reads the workspace's 128-byte header back before it launches: a workspace that does not hold the plan that
+ * returned `sizes` is SEB_ERR_INVALID and nothing is written.  Nothing is launched when entries_in == 0.  Nothing
+ * outside the sizes the plan returned is written, and on any index or workspace content nothing is read outside
+ * the runs' arrays (key_bytes, val_bytes[r], n entries): a stale index gives a wrong run, never an out-of-bounds
+ * access. */
+uint64_t seb_dev_runs_fold_workspace_size(uint64_t entries);
+int seb_dev_runs_fold_plan(const seb_run *runs, const void *const *index, const uint64_t *val_bytes, uint32_t num_runs,
+                           void *workspace, uint64_t workspace_bytes, seb_fold_sizes *sizes, void *stream);
+int seb_dev_runs_fold_emit(const seb_run *runs, const void *const *index, const uint8_t *const *vals,
+                           const uint64_t *val_bytes, uint32_t num_runs, const seb_fold_sizes *sizes,
+                           const void *workspace, uint64_t workspace_bytes, uint8_t *keys, uint64_t *key_off,
+                           uint8_t *out_vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq, void *stream);
+
+/* The host-buffer forms on a context; synchronous.
+ * seb_memtable_apply: one write batch.  Ops (keys / vals / val_off / deleted), first_seq and the active memtable's
+ * existing runs (num_runs <= SEB_MEM_MAX_RUNS - 1, newest first; their values are not needed) in host memory.  H2D,
+ * frame, seal, replay plan + emit of the image, index of the new run's keys, size delta, D2H.  Outputs: the sealed
+ * image (image_cap bytes; the caller's one Write to the log), the batch's run in six arrays (key_cap / val_cap bytes,
+ * entry_cap entries, key_off and val_off entry_cap + 1 offsets; seq nullable), *sizes = the replay's sizes of the
+ * batch, *size_delta = MemTable.size's change, *sequence = lsm.sequence after the batch (first_seq - 1 + n).  A
+ * capacity below a size: SEB_ERR_RANGE with *image_bytes and *sizes filled, so the caller can retry (the
+ * seb_wal_recover convention).  An existing run that fails its checks: SEB_ERR_INVALID, "run R: entry E".
+ * seb_memtable_fold: runs (with vals / val_bytes) in host memory into one run in host memory; same convention. */
+int seb_memtable_apply(seb_ctx *ctx, const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off,
+                       const uint8_t *deleted, uint64_t first_seq, const seb_run *runs, uint32_t num_runs,
+                       uint8_t *image, uint64_t image_cap, uint64_t *image_bytes, uint8_t *run_keys, uint64_t key_cap,
+                       uint64_t *run_key_off, uint8_t *run_vals, uint64_t val_cap, uint64_t *run_val_off,
+                       uint8_t *run_deleted, uint64_t *run_seq, uint64_t entry_cap, seb_replay_sizes *sizes,
+                       int64_t *size_delta, uint64_t *sequence);
+int seb_memtable_fold(seb_ctx *ctx, const seb_run *runs, const uint8_t *const *vals, const uint64_t *val_bytes,
+                      uint32_t num_runs, uint8_t *keys, uint64_t key_cap, uint64_t *key_off, uint8_t *out_vals,
+                      uint64_t val_cap, uint64_t *val_off, uint8_t *deleted, uint64_t *seq, uint64_t entry_cap,
+                      seb_fold_sizes *sizes);
+
 /* ---------- hash-index shard routing + WAL record checksums (off the bloom path) ---- */
 /* shard[i] = FNV-1a32(key i) & ((1 << shard_bits) - 1), the reference's getShard
  * (hashindex/shard.go:47-52; 256 shards = shard_bits 8).  hash[i] (nullable) = the full FNV-1a32.

@@ -8,6 +8,9 @@
 //   seb_sstable.cpp   the block-search, SSTable-builder and compaction-merge entry points
 //   seb_recover.cpp   the WAL replay's entry points and seb_wal_recover; the memtable lookup's and seb_memtable_get
 //   seb_memtable.cpp  the host half of the WAL replay and of the memtable lookup (no HIP dependency; seb_memtable.h)
+//   seb_write.cpp     the memtable write side's entry points, seb_memtable_apply and seb_memtable_fold
+//   seb_memwrite.cpp  the host half of the memtable write side (no HIP dependency; seb_memwrite.h)
+//   seb_memwrite.hip  its kernels: frame, size delta, fold
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -220,6 +223,8 @@ struct seb_ctx {
     seb::DevBuf mrg_in, mrg_ws, mrg_out;  // seb_merge: pool + blen + counts, the plan's workspace, the five output arrays
     seb::DevBuf rpl_in, rpl_ws, rpl_out;  // seb_wal_recover: image + offsets + ok, the plan's workspace, the six output arrays
     seb::DevBuf mg_runs, mg_out;  // seb_memtable_get: the runs' arrays and indexes, a chunk's six output arrays
+    seb::DevBuf mw_in, mw_img, mw_ws, mw_out, mw_runs;  // seb_memtable_apply / _fold: the ops + rec_off + delta, the image,
+                                                         // the plan's workspace, the run's six arrays, the runs + indexes
     seb::PinBuf hkeys, hbits;  // small filter builds: keys in, bits out, read and written by the kernels
     uint64_t chunk_bytes = 64ull << 20;
     std::vector<uint64_t> off_tmp[2];

@@ -282,6 +282,42 @@ hipError_t launch_runs_search(const KeyBatch &kb, const MemRunTab &tab, const Me
 hipError_t launch_get_join(const uint8_t *mem, const uint8_t *sst, uint64_t n, uint8_t *status, uint8_t *source,
                            hipStream_t s);
 
+// seb_memwrite.hip: the memtable's write side (lsm/lsm.go:97-137, lsm/wal.go:31-65, lsm/memtable.go:34-93): a Put /
+// Delete batch framed as WAL records, MemTable.size's change for a new run, and up to kMemRuns runs folded into one.
+constexpr uint32_t kWriteTile = 1024;  // ops per tile of the frame's scan, slots per tile of the fold's sums and emit
+constexpr uint32_t kScanWidth = 128;   // tiles per stretch of the scan over the tiles' sums (a carry between stretches)
+uint64_t frame_scratch_bytes(uint64_t n);  // device scratch of launch_frame_plan
+// n >= 1.  rec_off: n + 1 device u64.  Synchronises the stream; *image_bytes_host = the image's size; *err_host =
+// op << 1 | (0: its key offsets, 1: its value offsets) of the least bad op, all ones for none.
+hipError_t launch_frame_plan(const KeyBatch &kb, const uint64_t *val_off, const uint8_t *deleted, uint64_t *rec_off,
+                             void *scratch, uint64_t *image_bytes_host, uint64_t *err_host, hipStream_t s);
+// n >= 1, image_bytes >= 1.  Writes image[0, image_bytes) with every CRC field 0; nothing else is written.
+hipError_t launch_frame_emit(const KeyBatch &kb, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                             uint64_t first_seq, const uint64_t *rec_off, uint8_t *image, uint64_t image_bytes,
+                             hipStream_t s);
+// *delta (device) = MemTable.size's change when `fresh` (pre unused) goes in front of tab's runs.
+hipError_t launch_size_delta(const MemRun &fresh, const MemRunTab &tab, int64_t *delta, hipStream_t s);
+struct FoldTab {  // passed by value (kernel arguments)
+    MemRunTab tab;
+    const uint8_t *vals[kMemRuns];  // run r's value bytes
+    uint64_t val_bytes[kMemRuns];
+    uint64_t begin[kMemRuns + 1];   // run r's entries are [begin[r], begin[r+1]) of the union
+};
+// The fold's plan lives in a caller-provided workspace: a 128-byte header, the tiles' three sums, a 16-byte slot
+// per entry of the union.
+struct FoldWs {
+    uint64_t bytes, tiles, sums, slots;
+};
+FoldWs fold_ws_layout(uint64_t entries);
+// entries >= 1, < 2^32.  Synchronises; sizes_host = one seb_fold_sizes; *err_host = the least run whose val_off[n]
+// passes its val_bytes, all ones for none.
+hipError_t launch_fold_plan(const FoldTab &tab, uint64_t entries, void *ws, void *sizes_host, uint64_t *err_host,
+                            hipStream_t s);
+// *ok = the workspace's header is the plan's that returned `sizes`; reads the header back.
+hipError_t fold_ws_check(const void *sizes, const void *ws, bool *ok, hipStream_t s);
+hipError_t launch_fold_emit(const FoldTab &tab, const void *sizes, const void *ws, uint8_t *keys, uint64_t *key_off,
+                            uint8_t *vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

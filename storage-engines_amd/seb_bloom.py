@@ -70,6 +70,16 @@ class seb_replay_sizes(C.Structure):
                 self.max_sequence, self.memtable_size)
 
 
+class seb_fold_sizes(C.Structure):
+    _fields_ = [("entries_in", C.c_uint64), ("entries_out", C.c_uint64), ("key_bytes", C.c_uint64),
+                ("val_bytes", C.c_uint64), ("shadowed", C.c_uint64), ("tombstones", C.c_uint64),
+                ("max_sequence", C.c_uint64), ("memtable_size", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.entries_in, self.entries_out, self.key_bytes, self.val_bytes, self.shadowed, self.tombstones,
+                self.max_sequence, self.memtable_size)
+
+
 class seb_run(C.Structure):
     """A sorted run in the builder's input layout (the memtable lookup): host or device pointers per entry point."""
     _fields_ = [("keys", C.c_void_p), ("key_bytes", C.c_uint64), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
@@ -185,6 +195,25 @@ _SIGS = {
                                  _vp, _vp]),
     "seb_dev_get_join": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
     "seb_memtable_get": (_i, [_vp, C.POINTER(seb_keys), C.POINTER(seb_run), _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_wal_frame_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, C.POINTER(_u64)]),
+    "seb_wal_frame_emit": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _u64, _vp, _u64]),
+    "seb_dev_wal_frame_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, C.POINTER(_u64), _vp]),
+    "seb_dev_wal_frame_emit": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "seb_run_size_delta": (_i, [C.POINTER(seb_run), C.POINTER(seb_run), _u32, C.POINTER(C.c_int64)]),
+    "seb_dev_run_size_delta": (_i, [C.POINTER(seb_run), C.POINTER(seb_run), C.POINTER(_vp), _u32, _vp, _vp]),
+    "seb_runs_fold_plan": (_i, [C.POINTER(seb_run), C.POINTER(_u64), _u32, C.POINTER(seb_fold_sizes)]),
+    "seb_runs_fold_emit": (_i, [C.POINTER(seb_run), C.POINTER(_vp), C.POINTER(_u64), _u32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                C.POINTER(seb_fold_sizes)]),
+    "seb_dev_runs_fold_workspace_size": (_u64, [_u64]),
+    "seb_dev_runs_fold_plan": (_i, [C.POINTER(seb_run), C.POINTER(_vp), C.POINTER(_u64), _u32, _vp, _u64,
+                                    C.POINTER(seb_fold_sizes), _vp]),
+    "seb_dev_runs_fold_emit": (_i, [C.POINTER(seb_run), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _u32,
+                                    C.POINTER(seb_fold_sizes), _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_memtable_apply": (_i, [_vp, C.POINTER(seb_keys), _vp, _vp, _vp, _u64, C.POINTER(seb_run), _u32, _vp, _u64,
+                                C.POINTER(_u64), _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(seb_replay_sizes),
+                                C.POINTER(C.c_int64), C.POINTER(_u64)]),
+    "seb_memtable_fold": (_i, [_vp, C.POINTER(seb_run), C.POINTER(_vp), C.POINTER(_u64), _u32, _vp, _u64, _vp, _vp, _u64,
+                               _vp, _vp, _vp, _u64, C.POINTER(seb_fold_sizes)]),
     "seb_workspace_bytes": (_u64, []),
     "seb_dev_or_slices": (_i, [_vp, _u32, _u64, _vp, _vp]),
     "seb_workspace_release": (_i, []),
@@ -469,6 +498,55 @@ class Ctx:
         out = _memget_out(kb.n)
         check(lib().seb_memtable_get(self._p, kb.ref, arr, len(runs), *[o.ctypes.data for o in out]))
         return tuple(o[: kb.n] for o in out)
+
+    def memtable_apply(self, keys, vals, val_off, deleted=None, first_seq: int = 1, runs=(), caps=None):
+        """One write batch from host memory (LSM.Put / LSM.Delete per op, in order): ops as wal_frame takes them,
+        `runs` the active memtable's existing host_run()s, newest first.  Returns (image u8, run, size_delta,
+        sequence) with run = (keys u8, key_off u64, vals u8, val_off u64, deleted u8, seq u64, replay sizes) of the
+        batch and sequence = lsm.sequence after it; caps = (image bytes, key bytes, value bytes, entries) fixes the
+        capacities instead of retrying with the sizes a too small first call reports."""
+        kb, va, vo, de = _ops_host_args(keys, vals, val_off, deleted)
+        arr = _run_array(list(runs))
+        ic, kc, vc, ec = caps if caps is not None else (0, 0, 0, 0)
+        sz, img_bytes, delta, seq_after = seb_replay_sizes(), _u64(0), C.c_int64(0), _u64(0)
+        while True:
+            image = np.zeros(max(ic, 1), np.uint8)
+            out = _replay_out(kc, vc, ec)
+            rc = lib().seb_memtable_apply(self._p, kb.ref, va.ctypes.data, vo.ctypes.data, None if de is None else de.ctypes.data,
+                                          first_seq, arr, len(runs), image.ctypes.data, ic, C.byref(img_bytes),
+                                          out[0].ctypes.data, kc, out[1].ctypes.data, out[2].ctypes.data, vc, out[3].ctypes.data,
+                                          out[4].ctypes.data, out[5].ctypes.data, ec, C.byref(sz), C.byref(delta),
+                                          C.byref(seq_after))
+            if rc == -4 and caps is None and (img_bytes.value > ic or sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
+                ic, kc, vc, ec = img_bytes.value, sz.key_bytes, sz.val_bytes, sz.entries_out
+                continue
+            if rc < 0:  # SEB_ERR_RANGE fills the sizes: the exception carries them
+                err = SebError(rc, last_error())
+                err.sizes = sz.as_tuple()
+                err.image_bytes = img_bytes.value
+                raise err
+            return image[: img_bytes.value], _replay_trim(out, sz), delta.value, seq_after.value
+
+    def memtable_fold(self, runs, vals, caps=None):
+        """Fold host_run()s (newest first; vals[r] = run r's value bytes) into the one run GetAllEntries() returns:
+        (keys u8, key_off u64, vals u8, val_off u64, deleted u8, seq u64, fold sizes); caps = (key bytes, value
+        bytes, entries)."""
+        arr, vp, vb, keep = _fold_host_args(runs, vals)
+        kc, vc, ec = caps if caps is not None else (0, 0, 0)
+        sz = seb_fold_sizes()
+        while True:
+            out = _replay_out(kc, vc, ec)
+            rc = lib().seb_memtable_fold(self._p, arr, vp, vb, len(runs), out[0].ctypes.data, kc, out[1].ctypes.data,
+                                         out[2].ctypes.data, vc, out[3].ctypes.data, out[4].ctypes.data, out[5].ctypes.data,
+                                         ec, C.byref(sz))
+            if rc == -4 and caps is None and (sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
+                kc, vc, ec = sz.key_bytes, sz.val_bytes, sz.entries_out
+                continue
+            if rc < 0:
+                err = SebError(rc, last_error())
+                err.sizes = sz.as_tuple()
+                raise err
+            return _replay_trim(out, sz)
 
     def probe_multi(self, keys, filters: list[tuple[np.ndarray, int, int]]) -> np.ndarray:
         kb = as_keys(keys)
@@ -1393,6 +1471,172 @@ def memtable_get(keys, runs, device: int = 0):
     ctx = Ctx(device)
     try:
         return ctx.memtable_get(keys, runs)
+    finally:
+        ctx.close()
+
+
+# ------------------------------- memtable write side (lsm/lsm.go:97-137, lsm/wal.go:31-65, lsm/memtable.go:34-93)
+
+def _ops_host_args(keys, vals, val_off, deleted):
+    kb = as_keys(keys)
+    va = _wal_image_arg(vals)
+    vo = np.ascontiguousarray(val_off, dtype=np.uint64)
+    if vo.size != kb.n + 1:
+        raise ValueError(f"val_off holds {vo.size} offsets, {kb.n} ops need {kb.n + 1}")
+    de = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+    if de is not None and de.size < kb.n:
+        raise ValueError(f"deleted holds {de.size} bytes, the batch has {kb.n} ops")
+    return kb, va, vo, de
+
+
+def wal_frame_plan(keys, val_off, deleted=None) -> tuple[np.ndarray, int]:
+    """The host half's plan of a Put / Delete batch: (rec_off u64 of n + 1 boundaries, image bytes).  A key or a
+    value of 2^32 bytes or more, or offsets that decrease: SebError (INVALID) naming "op I"."""
+    kb = as_keys(keys)
+    vo = np.ascontiguousarray(val_off, dtype=np.uint64)
+    de = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+    off, total = np.zeros(kb.n + 1, np.uint64), _u64(0)
+    check(lib().seb_wal_frame_plan(kb.ref, vo.ctypes.data, None if de is None else de.ctypes.data, off.ctypes.data,
+                                   C.byref(total)))
+    return off, total.value
+
+
+def wal_frame(keys, vals, val_off, deleted=None, first_seq: int = 1) -> tuple[np.ndarray, np.ndarray]:
+    """The host half: the batch as WAL.Append's sealed records, op i with sequence first_seq + i (a Delete with no
+    value and deleted = 1): (image u8, rec_off u64)."""
+    kb, va, vo, de = _ops_host_args(keys, vals, val_off, deleted)
+    off, total = wal_frame_plan(kb, vo, de)
+    image = np.zeros(max(total, 1), np.uint8)
+    check(lib().seb_wal_frame_emit(kb.ref, va.ctypes.data, vo.ctypes.data, None if de is None else de.ctypes.data, first_seq,
+                                   image.ctypes.data, total))
+    return image[:total], off
+
+
+def dev_wal_frame_plan(keys: seb_keys, val_off, deleted, rec_off, stream=None) -> int:
+    """Device form: rec_off (n + 1 u64, a 64-bit tensor) is written; synchronises and returns the image's size."""
+    if keys.n and (rec_off is None or _nbytes(rec_off) < 8 * (keys.n + 1)):
+        raise ValueError(f"rec_off holds fewer than {keys.n + 1} offsets")
+    total = _u64(0)
+    check(lib().seb_dev_wal_frame_plan(C.byref(keys), _ptr(val_off), _ptr(deleted), _ptr(rec_off), C.byref(total),
+                                       _stream(stream)))
+    return total.value
+
+
+def dev_wal_frame_emit(keys: seb_keys, vals, val_off, deleted, first_seq: int, rec_off, image, image_bytes: int | None = None,
+                       stream=None) -> None:
+    """Device form: the sealed image into `image` (u8 tensor or view, any alignment); rec_off and image_bytes as
+    dev_wal_frame_plan left them.  Not synchronised."""
+    total = (_nbytes(image) if image is not None else 0) if image_bytes is None else image_bytes
+    if total and _nbytes(image) < total:
+        raise ValueError(f"image holds {_nbytes(image)} bytes, the plan needs {total}")
+    check(lib().seb_dev_wal_frame_emit(C.byref(keys), _ptr(vals), _ptr(val_off), _ptr(deleted), first_seq, _ptr(rec_off),
+                                       _ptr(image), total, _stream(stream)))
+
+
+def run_size_delta(fresh: seb_run, runs) -> int:
+    """The host half: MemTable.size's change when the host_run() `fresh` goes in front of the active memtable's
+    `runs` (host_run()s, newest first, at most MEM_MAX_RUNS - 1)."""
+    d = C.c_int64(0)
+    check(lib().seb_run_size_delta(C.byref(fresh), _run_array(list(runs)), len(runs), C.byref(d)))
+    return d.value
+
+
+def dev_run_size_delta(fresh: seb_run, runs, indexes, delta, stream=None) -> None:
+    """Device form: dev_run()s and the existing runs' index tensors; delta: one int64 on the device.  Not synchronised."""
+    if len(runs) != len(indexes):
+        raise ValueError("one index per run")
+    if delta is None or _nbytes(delta) < 8:
+        raise ValueError("delta holds fewer than 8 bytes")
+    ix = (_vp * max(len(runs), 1))(*[_ptr(t) for t in indexes])
+    check(lib().seb_dev_run_size_delta(C.byref(fresh), _run_array(list(runs)), ix, len(runs), _ptr(delta), _stream(stream)))
+
+
+def _fold_host_args(runs, vals):
+    if len(runs) != len(vals):
+        raise ValueError("one value array per run")
+    keep = [_wal_image_arg(v) for v in vals]
+    vp = (_vp * max(len(runs), 1))(*[v.ctypes.data if v.size else None for v in keep])
+    vb = (_u64 * max(len(runs), 1))(*[v.size for v in keep])
+    return _run_array(list(runs)), vp, vb, keep
+
+
+def runs_fold_plan(runs, vals) -> tuple[int, int, int, int, int, int, int, int]:
+    """The host half's plan: (entries_in, entries_out, key_bytes, val_bytes, shadowed, tombstones, max_sequence,
+    memtable_size) of the fold of host_run()s, newest first; vals[r] = run r's value bytes."""
+    arr, _, vb, keep = _fold_host_args(runs, vals)
+    sz = seb_fold_sizes()
+    check(lib().seb_runs_fold_plan(arr, vb, len(runs), C.byref(sz)))
+    return sz.as_tuple()
+
+
+def runs_fold(runs, vals, sizes=None):
+    """The host half: (keys u8, key_off u64, vals u8, val_off u64, deleted u8, seq u64, sizes) of the one run the
+    runs add up to; sizes default to runs_fold_plan's."""
+    arr, vp, vb, keep = _fold_host_args(runs, vals)
+    sz = seb_fold_sizes(*(runs_fold_plan(runs, vals) if sizes is None else sizes))
+    out = _replay_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
+    check(lib().seb_runs_fold_emit(arr, vp, vb, len(runs), out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data,
+                                   out[3].ctypes.data, out[4].ctypes.data, out[5].ctypes.data, C.byref(sz)))
+    return _replay_trim(out, sz)
+
+
+def dev_runs_fold_workspace_size(entries: int) -> int:
+    return lib().seb_dev_runs_fold_workspace_size(entries)
+
+
+def _fold_dev_args(runs, indexes, vals, val_bytes):
+    if len(runs) != len(indexes) or (vals is not None and len(vals) != len(runs)):
+        raise ValueError("one index and one value tensor per run")
+    ix = (_vp * max(len(runs), 1))(*[_ptr(t) for t in indexes])
+    if val_bytes is None:
+        val_bytes = [_nbytes(v) if v is not None else 0 for v in vals]
+    vb = (_u64 * max(len(runs), 1))(*val_bytes)
+    vp = None if vals is None else (_vp * max(len(runs), 1))(*[_ptr(v) for v in vals])
+    return _run_array(list(runs)), ix, vp, vb
+
+
+def dev_runs_fold_plan(runs, indexes, val_bytes, ws, ws_bytes: int | None = None, stream=None):
+    """Device form: dev_run()s (newest first), their index tensors and the bytes each run's values hold; ranks every
+    entry into the workspace tensor `ws` (dev_runs_fold_workspace_size(total entries) bytes); synchronises and
+    returns the sizes."""
+    arr, ix, _, vb = _fold_dev_args(runs, indexes, None, list(val_bytes))
+    sz = seb_fold_sizes()
+    check(lib().seb_dev_runs_fold_plan(arr, ix, vb, len(runs), _ptr(ws),
+                                       (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes, C.byref(sz),
+                                       _stream(stream)))
+    return sz.as_tuple()
+
+
+def dev_runs_fold_emit(runs, indexes, vals, sizes, ws, keys, key_off, out_vals, val_off, deleted, seq=None, val_bytes=None,
+                       stream=None) -> None:
+    """Device form: writes the folded run (sizes as dev_runs_fold_plan returned them); vals[r] = run r's value
+    tensor.  Not synchronised."""
+    sz = seb_fold_sizes(*sizes)
+    for name, t, size in (("keys", keys, sz.key_bytes), ("out_vals", out_vals, sz.val_bytes), ("deleted", deleted, sz.entries_out),
+                          ("key_off", key_off, 8 * (sz.entries_out + 1)), ("val_off", val_off, 8 * (sz.entries_out + 1)),
+                          ("seq", seq, 8 * sz.entries_out if seq is not None else 0)):
+        if (t is None and size) or (t is not None and _nbytes(t) < size):
+            raise ValueError(f"{name} holds {0 if t is None else _nbytes(t)} bytes, the plan needs {size}")
+    arr, ix, vp, vb = _fold_dev_args(runs, indexes, vals, val_bytes)
+    check(lib().seb_dev_runs_fold_emit(arr, ix, vp, vb, len(runs), C.byref(sz), _ptr(ws), _nbytes(ws) if ws is not None else 0,
+                                       _ptr(keys), _ptr(key_off), _ptr(out_vals), _ptr(val_off), _ptr(deleted), _ptr(seq),
+                                       _stream(stream)))
+
+
+def memtable_apply(keys, vals, val_off, deleted=None, first_seq: int = 1, runs=(), caps=None, device: int = 0):
+    """Ctx.memtable_apply on a context made for the call."""
+    ctx = Ctx(device)
+    try:
+        return ctx.memtable_apply(keys, vals, val_off, deleted, first_seq, runs, caps)
+    finally:
+        ctx.close()
+
+
+def memtable_fold(runs, vals, caps=None, device: int = 0):
+    """Ctx.memtable_fold on a context made for the call."""
+    ctx = Ctx(device)
+    try:
+        return ctx.memtable_fold(runs, vals, caps)
     finally:
         ctx.close()
 
