@@ -741,6 +741,89 @@ int seb_dev_get_join(const uint8_t *mem_status, const uint8_t *sst_status, uint6
 int seb_memtable_get(seb_ctx *ctx, const seb_keys *keys, const seb_run *runs, uint32_t num_runs, uint8_t *status,
                      uint8_t *run, uint32_t *entry, uint64_t *vloc, uint32_t *vlen, uint64_t *seq);
 
+/* ------------- Get path: only the keys the memtables leave undecided go on to the SSTable steps ---- */
+/* LSM.Get returns at the first memtable that holds the key, value or tombstone, and reads no filter, no index and
+ * no block for it (lsm/lsm.go:144-166).  For a batch that is a stream compaction between seb_dev_runs_search and
+ * the SSTable steps (seb_registry_multiget_list_dev, seb_registry_locate_dev, seb_dev_search_blocks,
+ * seb_dev_resolve_rows), which then run on m <= n keys, and a join that puts their answers back on the batch rows.
+ *
+ * Undecided keys: key i is undecided iff mem_status[i] is neither SEB_MEM_FOUND nor SEB_MEM_TOMBSTONE, whatever
+ * else the byte holds (3 and 255 count as undecided).  That is the rule by which seb_dev_get_join takes
+ * sst_status[i], so both pipelines give every status byte the same status.
+ *
+ * Compaction: the undecided keys in batch order (stable) become a dense batch of m = sizes->undecided keys, and
+ * row[j] (u32) = the batch index of compacted key j; row increases strictly.  A fixed-stride batch gives a
+ * fixed-stride batch of the same stride (key j at out_keys + j * stride; out_off is neither required nor
+ * written); a batch with offsets gives out_off[0..m], out_off[0] == 0 (whatever offsets[0] was), and
+ * sizes->key_bytes = the sum of the undecided keys' lengths = out_off[m].
+ *
+ * Row-mapped join, per batch key i:
+ *   SEB_MEM_FOUND      status SEB_GET_FOUND, source 0, vloc = mem_vloc[i], vlen = mem_vlen[i], col 0xFFFF
+ *   SEB_MEM_TOMBSTONE  status SEB_GET_MISS, source 0, vloc 0, vlen 0, col 0xFFFF
+ *   undecided          the j with row[j] == i: status = sst_status[j], source 1, vloc / vlen / col = sst_vloc[j] /
+ *                      sst_vlen[j] / sst_col[j], as seb_dev_resolve_rows wrote them for compacted key j
+ * and on bad input: an undecided key that no row names reads SEB_GET_MISS, source 1, 0, 0, 0xFFFF; a row[j] >= n
+ * or one naming a decided key is ignored (never an out-of-bounds or an overriding write); rows are expected to be
+ * distinct, and with duplicates which of them wins is unspecified.  mem_vloc, mem_vlen, sst_col, sst_vloc and
+ * sst_vlen are nullable and read as 0 (0xFFFF for sst_col); source, col, vloc and vlen are nullable.  status
+ * must not alias sst_status (they differ in length).  On status the result equals seb_dev_get_join over the
+ * whole batch's sst_status, and on source too for the three seb_mem_status values (seb_dev_get_join reports
+ * source 0 for a status byte above 2, this group 1: the SSTables' answer stands there). */
+typedef struct seb_compact_sizes {
+    uint64_t n;         /* keys->n */
+    uint64_t undecided; /* m: rows of the compacted batch */
+    uint64_t key_bytes; /* of the compacted batch: m * stride, or the sum of the undecided keys' lengths */
+    uint64_t reserved;  /* 0 */
+} seb_compact_sizes;
+
+/* Host only: keys in every seb_keys layout, everything in host memory.  *sizes is always filled.  out_keys,
+ * out_off and row all NULL: sizes only (the host's plan), and key_cap / row_cap are not looked at.  Otherwise
+ * row_cap < undecided or key_cap < key_bytes is SEB_ERR_RANGE with *sizes filled for the retry and nothing
+ * written; then row (where undecided != 0), out_keys (where key_bytes != 0) and out_off (iff keys->offsets is
+ * non-NULL) are required.  Writes row[0, undecided), out_off[0, undecided] and out_keys[0, key_bytes) and
+ * nothing else.  SEB_ERR_INVALID: a NULL required pointer (keys, sizes, mem_status where n != 0), offsets that
+ * decrease, keys->n >= 2^32.  n == 0 is valid.  It is the reference for the device form. */
+int seb_get_compact(const seb_keys *keys, const uint8_t *mem_status, seb_compact_sizes *sizes, uint8_t *out_keys,
+                    uint64_t key_cap, uint64_t *out_off, uint32_t *row, uint64_t row_cap);
+/* Host only: the row-mapped join above on host arrays.  Required: mem_status and status where n != 0, row and
+ * sst_status where m != 0 (else SEB_ERR_INVALID, nothing written); n >= 2^32: SEB_ERR_INVALID.  Writes the n
+ * elements of each non-NULL output and nothing else. */
+int seb_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_vloc, const uint32_t *mem_vlen, uint64_t n,
+                      const uint32_t *row, uint64_t m, const uint8_t *sst_status, const uint16_t *sst_col,
+                      const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source, uint16_t *col,
+                      uint64_t *vloc, uint32_t *vlen);
+
+/* Device pointers (offsets and out_off 8-byte aligned, row 4-byte aligned; keys in every seb_keys layout at any
+ * byte alignment, mem_status and out_keys at any byte alignment); `sizes` is HOST memory.  The workspace
+ * (seb_dev_get_compact_workspace_size(n) bytes of device memory, 16-byte aligned, opaque; 0 for n >= 2^32)
+ * carries the plan to the emit and must not be touched in between.
+ * seb_dev_get_compact_plan SYNCHRONISES and fills *sizes, so the caller can allocate (or check) the outputs.
+ * seb_dev_get_compact_emit (not synchronised; the same keys, mem_status and workspace) writes row[0, undecided),
+ * out_off[0, undecided] (required iff keys->offsets is non-NULL, else ignored) and out_keys[0, key_bytes).
+ * SEB_ERR_INVALID and nothing launched: a NULL required pointer (keys, sizes; mem_status and workspace where
+ * n != 0; for the emit row, out_off as above and out_keys where key_bytes != 0), keys->n >= 2^32, a misaligned
+ * pointer, a workspace below seb_dev_get_compact_workspace_size(n) (plan), sizes->n != keys->n, undecided > n or
+ * a key_bytes that is not undecided * stride for a fixed-stride batch (emit).  keys->n == 0, and for the emit
+ * sizes->undecided == 0: nothing is launched and nothing is written, out_off[0] included, SEB_OK (for n == 0 the
+ * plan sets *sizes to zeros and needs no workspace).
+ * Write bounds, whatever the inputs hold: the workspace's header carries a magic word, n, the tile count and the
+ * plan's two totals; where they do not match `sizes` the emit writes nothing.  Where mem_status changed between
+ * plan and emit the outputs may be wrong, but every store is clamped to the three ranges above.  Nothing is read
+ * outside the batch's keys as its offsets describe them, mem_status[0, n) and the workspace. */
+uint64_t seb_dev_get_compact_workspace_size(uint64_t n);
+int seb_dev_get_compact_plan(const seb_keys *keys, const uint8_t *mem_status, void *workspace, uint64_t workspace_bytes,
+                             seb_compact_sizes *sizes, void *stream);
+int seb_dev_get_compact_emit(const seb_keys *keys, const uint8_t *mem_status, const seb_compact_sizes *sizes,
+                             const void *workspace, uint8_t *out_keys, uint64_t *out_off, uint32_t *row, void *stream);
+/* The row-mapped join on device pointers, not synchronised: two launches in stream order, a lane per batch key
+ * (the memtables' answer or the "no row" default), then a lane per row.  Required pointers and refusals as the
+ * host form, also m >= 2^32.  n == 0: nothing is launched; m == 0: the first launch alone.  Nothing outside the n
+ * elements of each output is written, whatever row holds. */
+int seb_dev_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_vloc, const uint32_t *mem_vlen, uint64_t n,
+                          const uint32_t *row, uint64_t m, const uint8_t *sst_status, const uint16_t *sst_col,
+                          const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source,
+                          uint16_t *col, uint64_t *vloc, uint32_t *vlen, void *stream);
+
 /* ------------- memtable write side: Put / Delete batches into WAL records, the memtable's runs and the flush input ---- */
 /* What LSM.Put / LSM.Delete do to the log and to the active memtable (lsm/lsm.go:97-137, 203-235, lsm/wal.go:31-65,
  * lsm/memtable.go:34-93), for a batch of n ops applied in order by one writer, with lsm.sequence == S before it.

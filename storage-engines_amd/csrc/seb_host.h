@@ -11,6 +11,9 @@
 //   seb_write.cpp     the memtable write side's entry points, seb_memtable_apply and seb_memtable_fold
 //   seb_memwrite.cpp  the host half of the memtable write side (no HIP dependency; seb_memwrite.h)
 //   seb_memwrite.hip  its kernels: frame, size delta, fold
+//   seb_getpath.cpp   the host half of the Get path: compacting undecided keys, the row join (no HIP dependency;
+//                     seb_getpath.h); its entry points are in seb_recover.cpp beside the memtable lookup's
+//   seb_getpath.hip   its kernels: tile sums, scan, emit, the two join passes (the scan itself: seb_scan.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

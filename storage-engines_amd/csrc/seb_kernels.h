@@ -318,6 +318,25 @@ hipError_t fold_ws_check(const void *sizes, const void *ws, bool *ok, hipStream_
 hipError_t launch_fold_emit(const FoldTab &tab, const void *sizes, const void *ws, uint8_t *keys, uint64_t *key_off,
                             uint8_t *vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq, hipStream_t s);
 
+// seb_getpath.hip: the Get path (lsm/lsm.go:144-166): the keys the memtables leave undecided compacted into a dense
+// batch with a row map, and the SSTables' answers for those keys joined back onto their batch rows.  The plan lives
+// in a caller-provided workspace: a 128-byte header, then the tiles' two sums.
+constexpr uint32_t kGetTile = 1024;  // keys per tile of the compaction's sums and emit
+uint64_t compact_ws_bytes(uint64_t n);
+// n >= 1, n < 2^32.  Synchronises the stream; sizes_host = one seb_compact_sizes.
+hipError_t launch_compact_plan(const KeyBatch &kb, const uint8_t *mem_status, void *ws, void *sizes_host, hipStream_t s);
+// sizes: one seb_compact_sizes with n == kb.n >= 1; nothing is written unless ws holds the plan that returned it, and
+// nothing past row[undecided), out_off[undecided] and out_keys[key_bytes) in any case.  out_off is used only where
+// kb has offsets.
+hipError_t launch_compact_emit(const KeyBatch &kb, const uint8_t *mem_status, const void *sizes, const void *ws,
+                               uint8_t *out_keys, uint64_t *out_off, uint32_t *row, hipStream_t s);
+// Two launches in stream order: a lane per batch key, then a lane per row.  Nullable: mem_vloc, mem_vlen, sst_col,
+// sst_vloc, sst_vlen, source, col, vloc, vlen.
+hipError_t launch_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_vloc, const uint32_t *mem_vlen, uint64_t n,
+                                const uint32_t *row, uint64_t m, const uint8_t *sst_status, const uint16_t *sst_col,
+                                const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source,
+                                uint16_t *col, uint64_t *vloc, uint32_t *vlen, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

@@ -6,7 +6,8 @@
 //                  checked (one atomicMin keeps the least bad op), its record length is 21 + keyLen + (deleted ?
 //                  0 : valueLen), and a scan in the workgroup leaves rec_off relative to the tile
 //   k_write_scan   exclusive scan of per-tile sums, one workgroup of kScanWidth lanes per array with a carry
-//                  from one stretch of kScanWidth tiles to the next
+//                  from one stretch of kScanWidth tiles to the next (scan_tile_sums, seb_scan.h, shared with the Get
+//                  path's plan)
 //   k_frame_add    rec_off[i] += its tile's base; rec_off[n] = the image's size
 //   k_frame_emit   a lane per 16 aligned bytes of the image: a bisection of rec_off finds the record of its
 //                  first byte; a chunk that lies inside one key or one value and whose aligned source words lie
@@ -32,6 +33,7 @@
 
 #include "seb_kernels.h"
 #include "seb_keycmp.h"
+#include "seb_scan.h"
 
 namespace seb {
 
@@ -94,29 +96,7 @@ __device__ __forceinline__ void store16(uint64_t at, uint64_t w0, uint64_t w1) {
 
 // x[a * count ..] = its exclusive scan in place, total[a] = its sum; workgroup a takes array a
 __global__ __launch_bounds__(SW) void k_write_scan(uint64_t *x, uint64_t count, uint64_t *total) {
-    __shared__ uint64_t X[SW];
-    __shared__ uint64_t carry_s;
-    const uint32_t tid = threadIdx.x;
-    x += (uint64_t)blockIdx.x * count;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (uint64_t base = 0; base < count; base += SW) {
-        const uint64_t v = base + tid < count ? x[base + tid] : 0;
-        X[tid] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < SW; d <<= 1) {
-            const uint64_t a = tid >= d ? X[tid - d] : 0;
-            __syncthreads();
-            X[tid] += a;
-            __syncthreads();
-        }
-        const uint64_t carry = carry_s;
-        if (base + tid < count) x[base + tid] = carry + X[tid] - v;
-        __syncthreads();
-        if (tid == SW - 1) carry_s = carry + X[tid];
-        __syncthreads();
-    }
-    if (tid == 0) total[blockIdx.x] = carry_s;
+    scan_tile_sums(x + (uint64_t)blockIdx.x * count, count, total + blockIdx.x);  // seb_scan.h
 }
 
 // ------------------------------------------------------------------ frame -------------------

@@ -1,8 +1,10 @@
 // seb_recover.cpp — the WAL replay's entry points: the C ABI over its host half (seb_memtable.cpp) and its
 // kernels (seb_replay.hip), and seb_wal_recover, ReadAll + recoverFromWAL on host buffers through a context.
-// Below them the batched memtable lookup's, over the same host file and seb_memget.hip, and seb_memtable_get.
+// Below them the batched memtable lookup's, over the same host file and seb_memget.hip, and seb_memtable_get;
+// beside those the Get path's (seb_getpath.cpp, seb_getpath.hip): the compaction of undecided keys and the row join.
 #include <new>
 
+#include "seb_getpath.h"
 #include "seb_host.h"
 #include "seb_memtable.h"
 
@@ -308,6 +310,103 @@ extern "C" int seb_dev_get_join(const uint8_t *mem_status, const uint8_t *sst_st
     enter();
     if (n && (!mem_status || !sst_status || !status)) return fail(SEB_ERR_INVALID, "%s: null argument", who);
     HIP_OR_FAIL(launch_get_join(mem_status, sst_status, n, status, source, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+// ------------------------------------------------ Get path: undecided keys on to the SSTable steps (lsm/lsm.go:144-166)
+
+static_assert(sizeof(seb_compact_sizes) == sizeof(seb::CompactSizes) && sizeof(seb_compact_sizes) == 32, "seb_compact_sizes layout");
+
+static int compact_rc(int rc, uint64_t bad, const seb_compact_sizes *sz, const char *who) {
+    switch (rc) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_INVALID, "%s: 2^32 keys or more", who);
+    case -3:
+        return fail(SEB_ERR_INVALID, "%s: offsets decrease at %llu", who, (unsigned long long)bad);
+    case -4:
+        return fail(SEB_ERR_RANGE, "%s: a capacity is below its size (%llu rows, %llu key bytes); retry with *sizes", who,
+                    (unsigned long long)sz->undecided, (unsigned long long)sz->key_bytes);
+    default:
+        return fail(SEB_ERR_INVALID, "%s: a null argument", who);
+    }
+}
+
+extern "C" int seb_get_compact(const seb_keys *keys, const uint8_t *mem_status, seb_compact_sizes *sizes, uint8_t *out_keys,
+                               uint64_t key_cap, uint64_t *out_off, uint32_t *row, uint64_t row_cap) {
+    const char *who = "seb_get_compact";
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    uint64_t bad = 0;
+    rc = seb::get_compact(seb::KeysView{keys->data, keys->offsets, keys->n, keys->stride}, mem_status,
+                          (seb::CompactSizes *)sizes, out_keys, key_cap, out_off, row, row_cap, &bad);
+    return compact_rc(rc, bad, sizes, who);
+}
+
+extern "C" int seb_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_vloc, const uint32_t *mem_vlen, uint64_t n,
+                                 const uint32_t *row, uint64_t m, const uint8_t *sst_status, const uint16_t *sst_col,
+                                 const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source,
+                                 uint16_t *col, uint64_t *vloc, uint32_t *vlen) {
+    const int rc = seb::get_join_rows(mem_status, mem_vloc, mem_vlen, n, row, m, sst_status, sst_col, sst_vloc, sst_vlen,
+                                      status, source, col, vloc, vlen);
+    return compact_rc(rc, 0, nullptr, "seb_get_join_rows");
+}
+
+extern "C" uint64_t seb_dev_get_compact_workspace_size(uint64_t n) { return n >= (1ull << 32) ? 0 : compact_ws_bytes(n); }
+
+extern "C" int seb_dev_get_compact_plan(const seb_keys *keys, const uint8_t *mem_status, void *workspace,
+                                        uint64_t workspace_bytes, seb_compact_sizes *sizes, void *stream) {
+    const char *who = "seb_dev_get_compact_plan";
+    enter();
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    if (!sizes) return compact_rc(-1, 0, nullptr, who);
+    *sizes = seb_compact_sizes{keys->n, 0, 0, 0};
+    if (keys->n >= (1ull << 32)) return compact_rc(-2, 0, nullptr, who);
+    if (keys->n == 0) return SEB_OK;
+    if (!mem_status || !workspace) return compact_rc(-1, 0, nullptr, who);
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)keys->offsets & 7))
+        return fail(SEB_ERR_INVALID, "%s: the workspace is not 16-byte aligned, or the offsets are not 8-byte aligned", who);
+    const uint64_t want = compact_ws_bytes(keys->n);
+    if (workspace_bytes < want)
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes for %llu keys", who, (unsigned long long)workspace_bytes,
+                    (unsigned long long)want, (unsigned long long)keys->n);
+    HIP_OR_FAIL(launch_compact_plan(key_batch(keys), mem_status, workspace, sizes, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_get_compact_emit(const seb_keys *keys, const uint8_t *mem_status, const seb_compact_sizes *sizes,
+                                        const void *workspace, uint8_t *out_keys, uint64_t *out_off, uint32_t *row,
+                                        void *stream) {
+    const char *who = "seb_dev_get_compact_emit";
+    enter();
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    if (!sizes) return compact_rc(-1, 0, nullptr, who);
+    if (keys->n >= (1ull << 32)) return compact_rc(-2, 0, nullptr, who);
+    if (sizes->n != keys->n || sizes->undecided > sizes->n || (!keys->offsets && sizes->key_bytes != sizes->undecided * keys->stride))
+        return fail(SEB_ERR_INVALID, "%s: sizes are not this batch's plan", who);
+    if (keys->n == 0 || sizes->undecided == 0) return SEB_OK;
+    if (!mem_status || !workspace || !row || (keys->offsets && !out_off) || (sizes->key_bytes && !out_keys))
+        return compact_rc(-1, 0, nullptr, who);
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)keys->offsets & 7) || ((uintptr_t)out_off & 7) || ((uintptr_t)row & 3))
+        return fail(SEB_ERR_INVALID, "%s: the workspace is not 16-byte aligned, offsets or out_off not 8-byte aligned, or row "
+                    "not 4-byte aligned", who);
+    HIP_OR_FAIL(launch_compact_emit(key_batch(keys), mem_status, sizes, workspace, out_keys, out_off, row, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_vloc, const uint32_t *mem_vlen, uint64_t n,
+                                     const uint32_t *row, uint64_t m, const uint8_t *sst_status, const uint16_t *sst_col,
+                                     const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source,
+                                     uint16_t *col, uint64_t *vloc, uint32_t *vlen, void *stream) {
+    const char *who = "seb_dev_get_join_rows";
+    enter();
+    if (n >= (1ull << 32) || m >= (1ull << 32)) return compact_rc(-2, 0, nullptr, who);
+    if ((n && (!mem_status || !status)) || (m && (!row || !sst_status))) return compact_rc(-1, 0, nullptr, who);
+    HIP_OR_FAIL(launch_get_join_rows(mem_status, mem_vloc, mem_vlen, n, row, m, sst_status, sst_col, sst_vloc, sst_vlen, status,
+                                     source, col, vloc, vlen, (hipStream_t)stream));
     return SEB_OK;
 }
 

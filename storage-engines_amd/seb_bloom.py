@@ -80,6 +80,13 @@ class seb_fold_sizes(C.Structure):
                 self.max_sequence, self.memtable_size)
 
 
+class seb_compact_sizes(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("undecided", C.c_uint64), ("key_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.n, self.undecided, self.key_bytes)
+
+
 class seb_run(C.Structure):
     """A sorted run in the builder's input layout (the memtable lookup): host or device pointers per entry point."""
     _fields_ = [("keys", C.c_void_p), ("key_bytes", C.c_uint64), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
@@ -194,6 +201,12 @@ _SIGS = {
     "seb_dev_runs_search": (_i, [C.POINTER(seb_keys), C.POINTER(seb_run), C.POINTER(_vp), _u32, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp]),
     "seb_dev_get_join": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "seb_get_compact": (_i, [C.POINTER(seb_keys), _vp, C.POINTER(seb_compact_sizes), _vp, _u64, _vp, _vp, _u64]),
+    "seb_get_join_rows": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_dev_get_compact_workspace_size": (_u64, [_u64]),
+    "seb_dev_get_compact_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _u64, C.POINTER(seb_compact_sizes), _vp]),
+    "seb_dev_get_compact_emit": (_i, [C.POINTER(seb_keys), _vp, C.POINTER(seb_compact_sizes), _vp, _vp, _vp, _vp, _vp]),
+    "seb_dev_get_join_rows": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_memtable_get": (_i, [_vp, C.POINTER(seb_keys), C.POINTER(seb_run), _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_wal_frame_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, C.POINTER(_u64)]),
     "seb_wal_frame_emit": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _u64, _vp, _u64]),
@@ -1464,6 +1477,113 @@ def dev_get_join(mem_status, sst_status, n: int, status, source=None, stream=Non
         if t is not None and _nbytes(t) < n:
             raise ValueError(f"{name} holds {_nbytes(t)} bytes, {n} keys need {n}")
     check(lib().seb_dev_get_join(_ptr(mem_status), _ptr(sst_status), n, _ptr(status), _ptr(source), _stream(stream)))
+
+
+# ------------------------------- Get path: undecided keys on to the SSTable steps (lsm/lsm.go:144-166)
+
+def _np_ptr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def get_compact(keys, mem_status, caps: tuple[int, int] | None = None):
+    """The host half: the keys `mem_status` leaves undecided (neither MEM_FOUND nor MEM_TOMBSTONE), in batch order.
+    Returns (sizes, out_keys u8, out_off u64 or None for a fixed-stride batch, row u32); sizes = (n, undecided,
+    key_bytes).  caps = (key_cap, row_cap) sizes the outputs instead of a plan: a cap below its size raises SebError
+    (RANGE) with `.sizes` set for the retry."""
+    kb = as_keys(keys)
+    mem = np.ascontiguousarray(mem_status, dtype=np.uint8)
+    if mem.size != kb.n:
+        raise ValueError(f"mem_status holds {mem.size} bytes, the batch has {kb.n} keys")
+    sz = seb_compact_sizes()
+    if caps is None:
+        check(lib().seb_get_compact(kb.ref, _np_ptr(mem), C.byref(sz), None, 0, None, None, 0))
+        caps = (sz.key_bytes, sz.undecided)
+    key_cap, row_cap = caps
+    out_keys, row = np.zeros(max(key_cap, 1), np.uint8), np.zeros(max(row_cap, 1), np.uint32)
+    out_off = np.zeros(row_cap + 1, np.uint64) if kb.offsets is not None else None
+    rc = lib().seb_get_compact(kb.ref, _np_ptr(mem), C.byref(sz), out_keys.ctypes.data, key_cap,
+                               out_off.ctypes.data if out_off is not None else None, row.ctypes.data, row_cap)
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.sizes = sz.as_tuple()
+        raise err
+    return (sz.as_tuple(), out_keys[: sz.key_bytes], None if out_off is None else out_off[: sz.undecided + 1],
+            row[: sz.undecided])
+
+
+def get_join_rows(mem_status, row, sst_status, mem_vloc=None, mem_vlen=None, sst_col=None, sst_vloc=None, sst_vlen=None):
+    """The host half of the row-mapped join: sst_* are indexed by compacted key j and land on batch key row[j].
+    Returns (status u8, source u8, col u16, vloc u64, vlen u32), n elements each."""
+    mem = np.ascontiguousarray(mem_status, dtype=np.uint8)
+    rw = np.ascontiguousarray(row, dtype=np.uint32)
+    ss = np.ascontiguousarray(sst_status, dtype=np.uint8)
+    opt = lambda a, t: None if a is None else np.ascontiguousarray(a, dtype=t)  # noqa: E731
+    mvl, mvn = opt(mem_vloc, np.uint64), opt(mem_vlen, np.uint32)
+    sc, svl, svn = opt(sst_col, np.uint16), opt(sst_vloc, np.uint64), opt(sst_vlen, np.uint32)
+    n, m = mem.size, rw.size
+    for name, a, want in (("sst_status", ss, m), ("mem_vloc", mvl, n), ("mem_vlen", mvn, n), ("sst_col", sc, m),
+                          ("sst_vloc", svl, m), ("sst_vlen", svn, m)):
+        if a is not None and a.size != want:
+            raise ValueError(f"{name} holds {a.size} elements, not {want}")
+    n1 = max(n, 1)
+    out = (np.zeros(n1, np.uint8), np.zeros(n1, np.uint8), np.zeros(n1, np.uint16), np.zeros(n1, np.uint64),
+           np.zeros(n1, np.uint32))
+    check(lib().seb_get_join_rows(_np_ptr(mem), _np_ptr(mvl), _np_ptr(mvn), n, _np_ptr(rw), m, _np_ptr(ss), _np_ptr(sc),
+                                  _np_ptr(svl), _np_ptr(svn), *[o.ctypes.data for o in out]))
+    return tuple(o[:n] for o in out)
+
+
+def dev_get_compact_workspace_size(n: int) -> int:
+    return lib().seb_dev_get_compact_workspace_size(n)
+
+
+def dev_get_compact_plan(keys: seb_keys, mem_status, ws, ws_bytes: int | None = None, stream=None) -> seb_compact_sizes:
+    """Device form: counts the keys of the device batch `keys` that `mem_status` (n u8) leaves undecided, into the
+    workspace tensor `ws` (dev_get_compact_workspace_size(n) bytes, 16-byte aligned).  Synchronises; returns the
+    sizes (.n, .undecided, .key_bytes) that dev_get_compact_emit takes."""
+    if mem_status is not None and _nbytes(mem_status) < keys.n:
+        raise ValueError(f"mem_status holds {_nbytes(mem_status)} bytes, {keys.n} keys need {keys.n}")
+    sz = seb_compact_sizes()
+    check(lib().seb_dev_get_compact_plan(C.byref(keys), _ptr(mem_status), _ptr(ws), (_nbytes(ws) if ws is not None else 0)
+                                         if ws_bytes is None else ws_bytes, C.byref(sz), _stream(stream)))
+    return sz
+
+
+def dev_get_compact_emit(keys: seb_keys, mem_status, sizes: seb_compact_sizes, ws, out_keys, out_off, row, stream=None):
+    """Device form: writes the compacted batch into the caller's tensors out_keys (sizes.key_bytes u8, any
+    alignment), out_off (sizes.undecided + 1 u64; None for a fixed-stride batch) and row (sizes.undecided u32).
+    Returns (dev_keys over the compacted batch, row); not synchronised."""
+    m = sizes.undecided
+    for name, t, size in (("mem_status", mem_status, keys.n), ("out_keys", out_keys, sizes.key_bytes), ("row", row, 4 * m),
+                          ("out_off", out_off, 8 * (m + 1)),
+                          ("ws", ws, dev_get_compact_workspace_size(keys.n) if keys.n else 0)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, the plan needs {size}")
+    check(lib().seb_dev_get_compact_emit(C.byref(keys), _ptr(mem_status), C.byref(sizes), _ptr(ws), _ptr(out_keys),
+                                         _ptr(out_off), _ptr(row), _stream(stream)))
+    if keys.offsets:
+        ck = seb_keys(_ptr(out_keys), _ptr(out_off), m, 0, 0)
+    else:
+        ck = seb_keys(_ptr(out_keys), None, m, keys.stride, 0)
+    ck._keep = (out_keys, out_off)
+    return ck, row
+
+
+def dev_get_join_rows(mem_status, n: int, row, m: int, sst_status, status, source=None, col=None, vloc=None, vlen=None,
+                      mem_vloc=None, mem_vlen=None, sst_col=None, sst_vloc=None, sst_vlen=None, stream=None) -> None:
+    """Device form of the row-mapped join: the SSTable steps ran on the m compacted keys (sst_status, and optionally
+    sst_col / sst_vloc / sst_vlen, as dev_resolve_rows wrote them) and row (m u32) names each one's batch key.
+    Outputs: status (n u8) and optionally source (n u8), col (n u16), vloc (n u64), vlen (n u32).  Not
+    synchronised."""
+    for name, t, size in (("mem_status", mem_status, n), ("mem_vloc", mem_vloc, 8 * n), ("mem_vlen", mem_vlen, 4 * n),
+                          ("row", row, 4 * m), ("sst_status", sst_status, m), ("sst_col", sst_col, 2 * m),
+                          ("sst_vloc", sst_vloc, 8 * m), ("sst_vlen", sst_vlen, 4 * m), ("status", status, n),
+                          ("source", source, n), ("col", col, 2 * n), ("vloc", vloc, 8 * n), ("vlen", vlen, 4 * n)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {n} keys and {m} rows need {size}")
+    check(lib().seb_dev_get_join_rows(_ptr(mem_status), _ptr(mem_vloc), _ptr(mem_vlen), n, _ptr(row), m, _ptr(sst_status),
+                                      _ptr(sst_col), _ptr(sst_vloc), _ptr(sst_vlen), _ptr(status), _ptr(source), _ptr(col),
+                                      _ptr(vloc), _ptr(vlen), _stream(stream)))
 
 
 def memtable_get(keys, runs, device: int = 0):
