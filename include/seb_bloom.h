@@ -421,6 +421,86 @@ int seb_search_blocks(seb_ctx *ctx, const seb_keys *keys, const uint32_t *bid, u
 int seb_blocks_dedup(const uint64_t *files, const uint64_t *blocks, uint64_t cells, uint32_t *bid,
                      uint64_t *uniq_files, uint64_t *uniq_blocks, uint64_t uniq_cap, uint64_t *num_uniq);
 
+/* ------------- block ids: a located cell (slot, block offset) into an id of the block pool ---- */
+/* The step between seb_registry_locate_dev and seb_dev_search_blocks, on the cells as the list and the locate
+ * write them: cand[c] (u16 slot, 0xFFFF padding) and blocks[c] (u64, SEB_NO_BLOCK for none), c < cells = n * cap;
+ * a cell does not depend on its row.  cells >= 2^32 is SEB_ERR_INVALID.
+ *
+ * Residency table (nullable; res_slots == 0 without one): slot s is RESIDENT when s < res_slots and res_first[s]
+ * != SEB_NO_BLOCK_ID; its data section then lies in the pool as blocks res_first[s] .. res_first[s] +
+ * res_count[s] - 1 (what the device builder and the merge leave behind).
+ *
+ * Per cell, in this order:
+ *   1. cand == 0xFFFF or blocks == SEB_NO_BLOCK (either one): bid = SEB_NO_BLOCK_ID.
+ *   2. an offset >= 2^48: bid = SEB_NO_BLOCK_ID, counted in `bad` (no file is 256 TiB; the device packs
+ *      (slot, offset) into one 64-bit word).
+ *   3. a resident slot: with q = offset / 4096, bid = res_first[s] + q where offset % 4096 == 0, q < res_count[s]
+ *      and the sum is below 2^32 - 1; otherwise SEB_NO_BLOCK_ID, counted in `bad`: nothing is ever read for it.
+ *   4. otherwise a MISS: bid = id_base + r, r = the rank of the cell's (slot, offset) pair among the distinct miss
+ *      pairs in order of first appearance by cell index.  uniq_slot[r] (u16) and uniq_block[r] (u64) are the read
+ *      list: the caller reads block r into pool block id_base + r.  id_base + uniq > 2^32 - 1: SEB_ERR_INVALID.
+ * The same offset in two slots is two blocks.  With no residency table and file numbers for slots, bid and the
+ * read list are seb_blocks_dedup's, element for element.  The caller owns the pool and chooses id_base. */
+typedef struct seb_blockids_sizes {
+    uint64_t cells;
+    uint64_t resident; /* cells that rule 3 gave an id */
+    uint64_t misses;   /* cells of rule 4 */
+    uint64_t uniq;     /* distinct miss pairs: the read list's length */
+    uint64_t bad;      /* cells refused by rule 2 or 3 */
+    uint64_t reserved; /* 0 */
+} seb_blockids_sizes;
+
+/* Host only, and the reference for the device forms.  *sizes is filled whenever the arguments are valid.  bid,
+ * uniq_slot and uniq_block all NULL: the sizes only (uniq_cap and id_base are not looked at).  Otherwise uniq_cap <
+ * uniq is SEB_ERR_RANGE with *sizes filled for the retry and nothing else meaningful; then bid (where cells != 0)
+ * and uniq_slot / uniq_block (where uniq != 0) are required.  Writes bid[0, cells), uniq_slot[0, uniq) and
+ * uniq_block[0, uniq) and nothing else.  SEB_ERR_INVALID: a NULL required pointer (sizes; cand and blocks where
+ * cells != 0; res_first and res_count where res_slots != 0), cells >= 2^32, id_base + uniq > 2^32 - 1.
+ * cells == 0 is valid. */
+int seb_block_ids(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                  const uint32_t *res_count, uint32_t res_slots, uint32_t id_base, uint32_t *bid, uint16_t *uniq_slot,
+                  uint64_t *uniq_block, uint64_t uniq_cap, seb_blockids_sizes *sizes);
+
+/* Device pointers (blocks, uniq_block and counts 8-byte aligned, res_first, res_count and bid 4-byte aligned, cand
+ * and uniq_slot 2-byte aligned; else SEB_ERR_INVALID).  Not synchronised.  One kernel that applies rules 1-3 to
+ * every cell; a miss cell gets SEB_NO_BLOCK_ID.  counts (nullable): three u64 of device memory, set by the call
+ * to resident, misses and bad as in seb_blockids_sizes (cleared on the stream, then one add per wave).  This is the
+ * whole step for a tree whose files are all resident (misses == 0).  cells == 0: nothing is launched, counts is
+ * not written, SEB_OK.  Writes bid[0, cells) and counts[0, 3) and nothing else. */
+int seb_dev_block_ids_resident(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                               const uint32_t *res_count, uint32_t res_slots, uint32_t *bid, uint64_t *counts,
+                               void *stream);
+
+/* Every rule on device pointers (aligned as above), as the Get path's plan / emit pair; `sizes` is HOST memory.
+ * max_uniq is the caller's bound on the distinct miss pairs: the number of blocks in the files that are not
+ * resident is a good one, and `cells` always suffices (a larger value counts as `cells`).  The workspace
+ * (seb_dev_block_ids_workspace_size(cells, max_uniq) bytes of device memory, 16-byte aligned, opaque; 0 for cells
+ * >= 2^32) holds a table of the smallest power of two >= 2 * max_uniq slots; it carries the plan to the emit and
+ * must not be touched in between.
+ * seb_dev_block_ids_plan SYNCHRONISES and fills *sizes.  More than max_uniq distinct miss pairs: SEB_ERR_RANGE;
+ * sizes->misses (with resident and bad) is exact, sizes->uniq is some value above max_uniq (exact unless the table
+ * filled), and a retry with max_uniq = sizes->misses cannot fail this way.  A table that fills ends the probes; no
+ * lane ever waits for another.
+ * seb_dev_block_ids_emit (not synchronised; the same inputs, max_uniq and workspace) writes bid[0, cells),
+ * uniq_slot[0, uniq) and uniq_block[0, uniq) and nothing else.  No output depends on the hash or on scheduling.
+ * SEB_ERR_INVALID and nothing launched: a NULL required pointer (sizes; cand, blocks and the workspace where cells
+ * != 0; res_first and res_count where res_slots != 0; for the emit bid, and uniq_slot / uniq_block where uniq != 0),
+ * cells >= 2^32, a misaligned pointer, a workspace below seb_dev_block_ids_workspace_size (plan); for the emit
+ * sizes->cells != cells, sizes->uniq above max_uniq or above sizes->misses, resident + misses + bad > cells, or
+ * id_base + uniq > 2^32 - 1.  cells == 0: nothing is launched or written, SEB_OK (the plan sets *sizes to zeros and
+ * needs no workspace).
+ * Write bounds, whatever the inputs hold: the workspace's header carries a magic word, cells, the table size,
+ * max_uniq and the plan's totals; where they do not match `sizes` the emit writes nothing.  Where the inputs changed
+ * between plan and emit the outputs may be wrong, but every store stays inside the three ranges above. */
+uint64_t seb_dev_block_ids_workspace_size(uint64_t cells, uint64_t max_uniq);
+int seb_dev_block_ids_plan(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                           const uint32_t *res_count, uint32_t res_slots, uint64_t max_uniq, void *workspace,
+                           uint64_t workspace_bytes, seb_blockids_sizes *sizes, void *stream);
+int seb_dev_block_ids_emit(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                           const uint32_t *res_count, uint32_t res_slots, uint64_t max_uniq, uint32_t id_base,
+                           const seb_blockids_sizes *sizes, const void *workspace, uint32_t *bid, uint16_t *uniq_slot,
+                           uint64_t *uniq_block, void *stream);
+
 /* ------------- batched SSTable builder: data blocks, index block, metadata and the file image ---- */
 /* What SSTableBuilder computes between its Write calls (lsm/sstable_builder.go:42-135,185-290), for a sorted
  * run that is already in memory: entry i has key i of `keys`, value vals[val_off[i], val_off[i+1]) (n + 1

@@ -14,6 +14,9 @@
 //   seb_getpath.cpp   the host half of the Get path: compacting undecided keys, the row join (no HIP dependency;
 //                     seb_getpath.h); its entry points are in seb_recover.cpp beside the memtable lookup's
 //   seb_getpath.hip   its kernels: tile sums, scan, emit, the two join passes (the scan itself: seb_scan.h)
+//   seb_blockids.cpp  the host half of the block-id step: located cells into ids of the block pool (no HIP
+//                     dependency; seb_blockids.h); its entry points are in seb_sstable.cpp beside seb_blocks_dedup
+//   seb_blockids.hip  its kernels: the resident map, the miss pairs' table, flags, scan, rank, emit
 #pragma once
 #include <hip/hip_runtime.h>
 

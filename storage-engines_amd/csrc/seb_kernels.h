@@ -337,6 +337,30 @@ hipError_t launch_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_v
                                 const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source,
                                 uint16_t *col, uint64_t *vloc, uint32_t *vlen, hipStream_t s);
 
+// seb_blockids.hip: the block-id step between the locate and the block search (the rules: seb_blockids.h).  The
+// miss path's plan lives in a caller-provided workspace: a 128-byte header, an open-addressing table of the smallest
+// power of two >= 2 * max_uniq slots (pair u64, least cell index u32, rank u32), then the tiles' sums.
+constexpr uint32_t kBidTile = 1024;  // cells per tile of the first-appearance sums and ranks
+// the bound the table is sized by: max_uniq, or cells where that is less
+uint64_t blockids_max_uniq(uint64_t cells, uint64_t max_uniq);
+uint64_t blockids_ws_bytes(uint64_t cells, uint64_t max_uniq);
+// cells >= 1, < 2^32.  One kernel; counts (nullable, three device u64: resident, misses, bad) is cleared on the
+// stream first.
+hipError_t launch_blockids_resident(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                                    const uint32_t *res_count, uint32_t res_slots, uint32_t *bid, uint64_t *counts,
+                                    hipStream_t s);
+// cells >= 1, < 2^32.  Synchronises the stream; sizes_host = one seb_blockids_sizes; *overflow = the table filled
+// (sizes' uniq is then max_uniq + 1, not a count).
+hipError_t launch_blockids_plan(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                                const uint32_t *res_count, uint32_t res_slots, uint64_t max_uniq, void *ws,
+                                void *sizes_host, bool *overflow, hipStream_t s);
+// sizes: one seb_blockids_sizes; nothing is written unless ws holds the plan that returned it, and nothing outside
+// bid[cells), uniq_slot[uniq) and uniq_block[uniq) in any case.
+hipError_t launch_blockids_emit(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                                const uint32_t *res_count, uint32_t res_slots, uint64_t max_uniq, uint32_t id_base,
+                                const void *sizes, const void *ws, uint32_t *bid, uint16_t *uniq_slot, uint64_t *uniq_block,
+                                hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

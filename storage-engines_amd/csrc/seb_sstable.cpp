@@ -1,9 +1,11 @@
 // seb_sstable.cpp — the entry points of the batched data-block search, of the batched SSTable
 // builder and of the batched compaction merge: the C ABI over their host halves (seb_block.cpp) and
 // their kernels (seb_search.hip, seb_sst.hip, seb_merge.hip), and the host-buffer forms through a context.
+// Also the block-id step that feeds the search (seb_blockids.cpp, seb_blockids.hip).
 #include <new>
 
 #include "seb_block.h"
+#include "seb_blockids.h"
 #include "seb_host.h"
 
 using namespace seb;
@@ -34,6 +36,114 @@ extern "C" int seb_blocks_dedup(const uint64_t *files, const uint64_t *blocks, u
     default:
         return fail(SEB_ERR_INVALID, "seb_blocks_dedup: null argument");
     }
+}
+
+// ------------------------------------------------ block ids: (slot, block offset) cells into ids of the block pool
+
+static_assert(sizeof(seb_blockids_sizes) == sizeof(seb::BlockIdSizes) && sizeof(seb_blockids_sizes) == 48, "seb_blockids_sizes layout");
+
+static int blockids_rc(int rc, const seb_blockids_sizes *sz, uint64_t cap, const char *who) {
+    switch (rc) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_INVALID, "%s: 2^32 cells or more", who);
+    case -3:
+        return fail(SEB_ERR_NOMEM, "%s: out of host memory", who);
+    case -4:
+        return fail(SEB_ERR_RANGE, "%s: %llu distinct miss pairs > %llu; retry with *sizes", who,
+                    (unsigned long long)sz->uniq, (unsigned long long)cap);
+    case -5:
+        return fail(SEB_ERR_INVALID, "%s: id_base + %llu ids pass 2^32 - 1", who, (unsigned long long)sz->uniq);
+    default:
+        return fail(SEB_ERR_INVALID, "%s: a null argument", who);
+    }
+}
+
+extern "C" int seb_block_ids(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                             const uint32_t *res_count, uint32_t res_slots, uint32_t id_base, uint32_t *bid,
+                             uint16_t *uniq_slot, uint64_t *uniq_block, uint64_t uniq_cap, seb_blockids_sizes *sizes) {
+    const int rc = seb::block_ids(cand, blocks, cells, res_first, res_count, res_slots, id_base, bid, uniq_slot, uniq_block,
+                                  uniq_cap, (seb::BlockIdSizes *)sizes);
+    return blockids_rc(rc, sizes, uniq_cap, "seb_block_ids");
+}
+
+// the device forms' common refusals; SEB_OK with cells == 0 is the caller's to return early on
+static int check_blockids_args(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                               const uint32_t *res_count, uint32_t res_slots, const char *who) {
+    if (cells >= (1ull << 32)) return blockids_rc(-2, nullptr, 0, who);
+    if ((cells && (!cand || !blocks)) || (res_slots && (!res_first || !res_count))) return blockids_rc(-1, nullptr, 0, who);
+    if (((uintptr_t)cand & 1) || ((uintptr_t)blocks & 7) || ((uintptr_t)res_first & 3) || ((uintptr_t)res_count & 3))
+        return fail(SEB_ERR_INVALID, "%s: cand is not 2-byte aligned, blocks not 8-byte or the residency table not 4-byte", who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_block_ids_resident(const uint16_t *cand, const uint64_t *blocks, uint64_t cells,
+                                          const uint32_t *res_first, const uint32_t *res_count, uint32_t res_slots,
+                                          uint32_t *bid, uint64_t *counts, void *stream) {
+    const char *who = "seb_dev_block_ids_resident";
+    enter();
+    int rc;
+    if ((rc = check_blockids_args(cand, blocks, cells, res_first, res_count, res_slots, who))) return rc;
+    if (cells == 0) return SEB_OK;
+    if (!bid) return blockids_rc(-1, nullptr, 0, who);
+    if (((uintptr_t)bid & 3) || ((uintptr_t)counts & 7))
+        return fail(SEB_ERR_INVALID, "%s: bid is not 4-byte aligned, or counts not 8-byte aligned", who);
+    HIP_OR_FAIL(launch_blockids_resident(cand, blocks, cells, res_first, res_count, res_slots, bid, counts, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" uint64_t seb_dev_block_ids_workspace_size(uint64_t cells, uint64_t max_uniq) {
+    return cells >= (1ull << 32) ? 0 : blockids_ws_bytes(cells, max_uniq);
+}
+
+extern "C" int seb_dev_block_ids_plan(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                                      const uint32_t *res_count, uint32_t res_slots, uint64_t max_uniq, void *workspace,
+                                      uint64_t workspace_bytes, seb_blockids_sizes *sizes, void *stream) {
+    const char *who = "seb_dev_block_ids_plan";
+    enter();
+    int rc;
+    if (!sizes) return blockids_rc(-1, nullptr, 0, who);
+    *sizes = seb_blockids_sizes{cells, 0, 0, 0, 0, 0};
+    if ((rc = check_blockids_args(cand, blocks, cells, res_first, res_count, res_slots, who))) return rc;
+    if (cells == 0) return SEB_OK;
+    if (!workspace) return blockids_rc(-1, nullptr, 0, who);
+    if ((uintptr_t)workspace & 15) return fail(SEB_ERR_INVALID, "%s: the workspace is not 16-byte aligned", who);
+    const uint64_t want = blockids_ws_bytes(cells, max_uniq);
+    if (workspace_bytes < want)
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes for %llu cells, max_uniq %llu", who,
+                    (unsigned long long)workspace_bytes, (unsigned long long)want, (unsigned long long)cells,
+                    (unsigned long long)max_uniq);
+    bool overflow = false;
+    HIP_OR_FAIL(launch_blockids_plan(cand, blocks, cells, res_first, res_count, res_slots, max_uniq, workspace, sizes, &overflow,
+                                     (hipStream_t)stream));
+    const uint64_t bound = blockids_max_uniq(cells, max_uniq);
+    if (overflow || sizes->uniq > bound) return blockids_rc(-4, sizes, bound, who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_block_ids_emit(const uint16_t *cand, const uint64_t *blocks, uint64_t cells, const uint32_t *res_first,
+                                      const uint32_t *res_count, uint32_t res_slots, uint64_t max_uniq, uint32_t id_base,
+                                      const seb_blockids_sizes *sizes, const void *workspace, uint32_t *bid,
+                                      uint16_t *uniq_slot, uint64_t *uniq_block, void *stream) {
+    const char *who = "seb_dev_block_ids_emit";
+    enter();
+    int rc;
+    if (!sizes) return blockids_rc(-1, nullptr, 0, who);
+    if ((rc = check_blockids_args(cand, blocks, cells, res_first, res_count, res_slots, who))) return rc;
+    if (sizes->cells != cells || sizes->uniq > blockids_max_uniq(cells, max_uniq) || sizes->uniq > sizes->misses ||
+        sizes->resident > cells || sizes->misses > cells || sizes->bad > cells ||
+        sizes->resident + sizes->misses + sizes->bad > cells)
+        return fail(SEB_ERR_INVALID, "%s: sizes are not these cells' plan", who);
+    if ((uint64_t)id_base + sizes->uniq > SEB_NO_BLOCK_ID) return blockids_rc(-5, sizes, 0, who);
+    if (cells == 0) return SEB_OK;
+    if (!workspace || !bid || (sizes->uniq && (!uniq_slot || !uniq_block))) return blockids_rc(-1, nullptr, 0, who);
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)bid & 3) || ((uintptr_t)uniq_slot & 1) || ((uintptr_t)uniq_block & 7))
+        return fail(SEB_ERR_INVALID, "%s: the workspace is not 16-byte aligned, bid not 4-byte, uniq_slot not 2-byte or "
+                    "uniq_block not 8-byte", who);
+    HIP_OR_FAIL(launch_blockids_emit(cand, blocks, cells, res_first, res_count, res_slots, max_uniq, id_base, sizes, workspace,
+                                     bid, uniq_slot, uniq_block, (hipStream_t)stream));
+    return SEB_OK;
 }
 
 static int check_search_args(const seb_keys *keys, const void *bid, uint32_t cap, const uint8_t *pool, const void *blen,

@@ -87,6 +87,14 @@ class seb_compact_sizes(C.Structure):
         return (self.n, self.undecided, self.key_bytes)
 
 
+class seb_blockids_sizes(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("resident", C.c_uint64), ("misses", C.c_uint64), ("uniq", C.c_uint64),
+                ("bad", C.c_uint64), ("reserved", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.cells, self.resident, self.misses, self.uniq, self.bad)
+
+
 class seb_run(C.Structure):
     """A sorted run in the builder's input layout (the memtable lookup): host or device pointers per entry point."""
     _fields_ = [("keys", C.c_void_p), ("key_bytes", C.c_uint64), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
@@ -170,6 +178,12 @@ _SIGS = {
     "seb_dev_resolve_rows": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "seb_search_blocks": (_i, [_vp, C.POINTER(seb_keys), _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "seb_blocks_dedup": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "seb_block_ids": (_i, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u64, C.POINTER(seb_blockids_sizes)]),
+    "seb_dev_block_ids_resident": (_i, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "seb_dev_block_ids_workspace_size": (_u64, [_u64, _u64]),
+    "seb_dev_block_ids_plan": (_i, [_vp, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _u64, C.POINTER(seb_blockids_sizes), _vp]),
+    "seb_dev_block_ids_emit": (_i, [_vp, _vp, _u64, _vp, _vp, _u32, _u64, _u32, C.POINTER(seb_blockids_sizes), _vp, _vp,
+                                    _vp, _vp, _vp]),
     "seb_sst_plan": (_i, [C.POINTER(seb_keys), _vp, C.POINTER(seb_sst_sizes)]),
     "seb_sst_encode": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(seb_sst_sizes)]),
     "seb_sst_footer": (_i, [_u64, _u64, _u64, _vp]),
@@ -1584,6 +1598,94 @@ def dev_get_join_rows(mem_status, n: int, row, m: int, sst_status, status, sourc
     check(lib().seb_dev_get_join_rows(_ptr(mem_status), _ptr(mem_vloc), _ptr(mem_vlen), n, _ptr(row), m, _ptr(sst_status),
                                       _ptr(sst_col), _ptr(sst_vloc), _ptr(sst_vlen), _ptr(status), _ptr(source), _ptr(col),
                                       _ptr(vloc), _ptr(vlen), _stream(stream)))
+
+
+# ------------------------------- block ids: located cells (slot, block offset) into ids of the block pool
+
+def block_ids(cand, blocks, res_first=None, res_count=None, id_base: int = 0, uniq_cap: int | None = None,
+              stream=None):
+    """The host half and the device forms' reference: cand (u16 slots, 0xFFFF padding) and blocks (u64 offsets,
+    NO_BLOCK for none) of one shape, and optionally the residency table (res_first / res_count u32 per slot,
+    res_first NO_BLOCK_ID for a file that is not resident).  Returns (sizes, bid u32 in the shape of cand, uniq_slot
+    u16, uniq_block u64); sizes = (cells, resident, misses, uniq, bad).  uniq_cap sizes the read list instead of a
+    sizes-only call: below `uniq` it raises SebError (RANGE) with `.sizes` set for the retry.  `stream` is accepted
+    for symmetry with the device forms and ignored: nothing here touches a device."""
+    cand = np.ascontiguousarray(cand, dtype=np.uint16)
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+    if cand.shape != blocks.shape:
+        raise ValueError("cand and blocks must have one shape")
+    rf = None if res_first is None else np.ascontiguousarray(res_first, dtype=np.uint32)
+    rc_ = None if res_count is None else np.ascontiguousarray(res_count, dtype=np.uint32)
+    if (rf is None) != (rc_ is None) or (rf is not None and rf.size != rc_.size):
+        raise ValueError("res_first and res_count must both be given, with one entry per slot")
+    slots = 0 if rf is None else rf.size
+    cells = cand.size
+    sz = seb_blockids_sizes()
+    if uniq_cap is None:
+        check(lib().seb_block_ids(_np_ptr(cand), _np_ptr(blocks), cells, _np_ptr(rf), _np_ptr(rc_), slots, id_base, None,
+                                  None, None, 0, C.byref(sz)))
+        uniq_cap = sz.uniq
+    bid = np.zeros(max(cells, 1), np.uint32)
+    us, ub = np.zeros(max(uniq_cap, 1), np.uint16), np.zeros(max(uniq_cap, 1), np.uint64)
+    rc = lib().seb_block_ids(_np_ptr(cand), _np_ptr(blocks), cells, _np_ptr(rf), _np_ptr(rc_), slots, id_base,
+                             bid.ctypes.data, us.ctypes.data, ub.ctypes.data, uniq_cap, C.byref(sz))
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.sizes = sz.as_tuple()
+        raise err
+    return sz.as_tuple(), bid[:cells].reshape(cand.shape), us[: sz.uniq], ub[: sz.uniq]
+
+
+def _blockids_check(cells, cand, blocks, res_first, res_count, res_slots, extra=()):
+    for name, t, size in (("cand", cand, 2 * cells), ("blocks", blocks, 8 * cells), ("res_first", res_first, 4 * res_slots),
+                          ("res_count", res_count, 4 * res_slots)) + tuple(extra):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {cells} cells and {res_slots} slots need {size}")
+
+
+def dev_block_ids_resident(cand, blocks, cells: int, res_first, res_count, res_slots: int, bid, counts=None,
+                           stream=None) -> None:
+    """Device form, one kernel: bid[c] (u32) = the pool id of cell c of a resident file (res_first[slot] + offset /
+    4096), NO_BLOCK_ID for padding, refused offsets and the cells of files that are not resident.  counts
+    (optional, three u64): resident, misses, bad.  Not synchronised."""
+    _blockids_check(cells, cand, blocks, res_first, res_count, res_slots, (("bid", bid, 4 * cells), ("counts", counts, 24)))
+    check(lib().seb_dev_block_ids_resident(_ptr(cand), _ptr(blocks), cells, _ptr(res_first), _ptr(res_count), res_slots,
+                                           _ptr(bid), _ptr(counts), _stream(stream)))
+
+
+def dev_block_ids_workspace_size(cells: int, max_uniq: int, stream=None) -> int:
+    return lib().seb_dev_block_ids_workspace_size(cells, max_uniq)
+
+
+def dev_block_ids_plan(cand, blocks, cells: int, res_first, res_count, res_slots: int, max_uniq: int, ws,
+                       ws_bytes: int | None = None, stream=None) -> seb_blockids_sizes:
+    """Device form: classifies the cells and numbers the distinct (slot, offset) pairs of the files that are not
+    resident, into the workspace tensor `ws` (dev_block_ids_workspace_size(cells, max_uniq) bytes, 16-byte
+    aligned).  Synchronises; returns the sizes that dev_block_ids_emit takes.  More than max_uniq distinct pairs
+    raises SebError (RANGE) with `.sizes` set: max_uniq = sizes.misses always suffices."""
+    _blockids_check(cells, cand, blocks, res_first, res_count, res_slots)
+    sz = seb_blockids_sizes()
+    rc = lib().seb_dev_block_ids_plan(_ptr(cand), _ptr(blocks), cells, _ptr(res_first), _ptr(res_count), res_slots, max_uniq,
+                                      _ptr(ws), (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes,
+                                      C.byref(sz), _stream(stream))
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.sizes = sz
+        raise err
+    return sz
+
+
+def dev_block_ids_emit(cand, blocks, cells: int, res_first, res_count, res_slots: int, max_uniq: int, id_base: int,
+                       sizes: seb_blockids_sizes, ws, bid, uniq_slot, uniq_block, stream=None) -> None:
+    """Device form: bid (cells u32) for every cell, a miss cell's id = id_base + its pair's rank, and the read list
+    uniq_slot (sizes.uniq u16) / uniq_block (sizes.uniq u64).  The same inputs, max_uniq and workspace as the plan.
+    Not synchronised."""
+    _blockids_check(cells, cand, blocks, res_first, res_count, res_slots,
+                    (("bid", bid, 4 * cells), ("uniq_slot", uniq_slot, 2 * sizes.uniq), ("uniq_block", uniq_block, 8 * sizes.uniq),
+                     ("ws", ws, dev_block_ids_workspace_size(cells, max_uniq) if cells else 0)))
+    check(lib().seb_dev_block_ids_emit(_ptr(cand), _ptr(blocks), cells, _ptr(res_first), _ptr(res_count), res_slots, max_uniq,
+                                       id_base, C.byref(sizes), _ptr(ws), _ptr(bid), _ptr(uniq_slot), _ptr(uniq_block),
+                                       _stream(stream)))
 
 
 def memtable_get(keys, runs, device: int = 0):
