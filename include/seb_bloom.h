@@ -904,6 +904,84 @@ int seb_dev_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_vloc, c
                           const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source,
                           uint16_t *col, uint64_t *vloc, uint32_t *vlen, void *stream);
 
+/* ------------- Get values: a batch's found values gathered into one dense buffer ---- */
+/* LSM.Get returns the value: searchBlock's make([]byte, valueSize) + copy (lsm/sstable.go:276-278), or the memtable
+ * entry's Value (lsm/lsm.go:146-152, 157-163, 175-180).  The Get path above ends with a location per key; this
+ * group does the copy for a batch: the found keys' values back to back in batch order, with an offset array, so a
+ * GetBatch is one D2H copy away from its answer.
+ *
+ * Inputs per batch key i: status[i] (seb_get_status), source[i] (0: the memtables decided; 1: the block pool holds
+ * the value), vloc[i] (u64), vlen[i] (u32), as seb_dev_get_join_rows writes them, and run[i] (u8), the deciding
+ * run as seb_dev_runs_search writes it; run is looked at only where source[i] == 0, may be NULL iff num_runs <= 1
+ * and is then read as 0.  (Pipeline A's seb_dev_get_join + seb_dev_resolve_rows arrays also work, with the
+ * memtables' vloc / vlen merged in by the caller.)
+ * Sources: vals[r][0, val_bytes[r]) for r < num_runs <= SEB_MEM_MAX_RUNS, the runs' value bytes as
+ * seb_dev_runs_fold_emit takes them (vloc is the entry's val_off, an offset from vals[r]; vals[r] may be NULL only
+ * where val_bytes[r] == 0), and pool[0, pool_bytes), the block pool (vloc = bid * 4096 + voff; pool may be NULL iff
+ * pool_bytes == 0).  num_runs == 0 is valid.
+ *
+ * Key i carries a value iff status[i] == SEB_GET_FOUND exactly.  Every other status byte (MISS, ERROR, 3, 255)
+ * contributes 0 bytes, and its source, run, vloc and vlen are never used to form an address, whatever they hold.
+ * A carrying key is valid iff
+ *   source == 0, run[i] < num_runs, vloc <= val_bytes[r] and vlen <= val_bytes[r] - vloc (compared this way round,
+ *                so nothing wraps), and vals[r] is not a NULL with val_bytes[r] != 0; or
+ *   source == 1, vloc <= pool_bytes and vlen <= pool_bytes - vloc (a pool value is NOT required to lie inside one
+ *                4 KiB block: the resolve guarantees that, this step does not re-check it).
+ * Any other source byte is invalid.  INVALID CARRYING KEYS ARE REFUSED, NOT SKIPPED: SEB_ERR_INVALID, and
+ * seb_last_error names the lowest such key ("key K"); *sizes then holds n alone and no emit may follow.  (The
+ * rule seb_dev_run_index applies to runs; a skipped value would be a Get that silently returns the wrong bytes.)
+ *
+ * Outputs: out_off[0..n] (u64), out_off[0] = 0 and out_off[i + 1] - out_off[i] = vlen[i] for a carrying key, else
+ * 0; out_vals[0, out_off[n]) = the values back to back.  A found empty value and a miss both have an empty span;
+ * status tells them apart. */
+typedef struct seb_values_sizes {
+    uint64_t n;         /* batch keys */
+    uint64_t found;     /* carrying keys */
+    uint64_t val_bytes; /* the sum of their vlen = out_off[n] */
+    uint64_t reserved;  /* 0 */
+} seb_values_sizes;
+
+/* Host only: everything in host memory.  *sizes is always filled.  out_off and out_vals both NULL: sizes only (the
+ * host's plan), and val_cap is not looked at.  Otherwise val_cap < val_bytes is SEB_ERR_RANGE with *sizes filled
+ * for the retry and nothing written (seb_get_compact's convention); then out_off is required, and out_vals where
+ * val_bytes != 0.  Writes out_off[0, n] and out_vals[0, val_bytes) and nothing else.  SEB_ERR_INVALID: the refusal
+ * above, a NULL required pointer (sizes; status, source, vloc and vlen where n != 0; run where num_runs > 1; vals and
+ * val_bytes where num_runs != 0; pool where pool_bytes != 0), num_runs > SEB_MEM_MAX_RUNS, n >= 2^32.  n == 0 is
+ * valid.  It is the reference for the device form and what a caller without a GPU uses.
+ * There is no host-buffer form on a seb_ctx: it would upload the whole pool for one gather. */
+int seb_get_values(const uint8_t *status, const uint8_t *source, const uint8_t *run, const uint64_t *vloc,
+                   const uint32_t *vlen, uint64_t n, const uint8_t *const *vals, const uint64_t *val_bytes,
+                   uint32_t num_runs, const uint8_t *pool, uint64_t pool_bytes, seb_values_sizes *sizes,
+                   uint64_t *out_off, uint8_t *out_vals, uint64_t val_cap);
+
+/* Device pointers (vloc and out_off 8-byte aligned, vlen 4-byte aligned; status, source, run, the sources and
+ * out_vals at any byte alignment); `vals` and `val_bytes` are HOST arrays of num_runs elements holding device
+ * pointers and sizes, like `runs` / `index` in seb_dev_runs_search; `sizes` is HOST memory.  The workspace
+ * (seb_dev_get_values_workspace_size(n) bytes of device memory, 16-byte aligned, opaque; 0 for n >= 2^32) carries
+ * the plan to the emit and must not be touched in between; the emit writes to it too.
+ * seb_dev_get_values_plan SYNCHRONISES, fills *sizes, and returns the refusal above.
+ * seb_dev_get_values_emit (not synchronised; the same inputs and workspace) writes out_off[0, n] and
+ * out_vals[0, val_bytes).  Where val_bytes == 0 out_off is still written (all zeros), out_vals may be NULL and no
+ * copy kernel is launched.  n == 0: nothing is launched and nothing is written, SEB_OK (the plan sets *sizes to
+ * zeros and needs no workspace).
+ * SEB_ERR_INVALID and nothing launched: a NULL required pointer (as the host form; the workspace where n != 0; for
+ * the emit out_off, and out_vals where val_bytes != 0), n >= 2^32, num_runs > SEB_MEM_MAX_RUNS, a misaligned
+ * pointer, a workspace below seb_dev_get_values_workspace_size(n) (plan), sizes->n != n or found > n (emit).
+ * Bounds, whatever the inputs hold: the workspace's header carries a magic word, n, the tile count, the plan's two
+ * totals and its refusal; where they do not match `sizes` the emit writes nothing.  The emit re-derives every
+ * source address from the inputs and checks it against its source, so where the inputs changed between plan and
+ * emit the outputs may be wrong, but nothing is read outside vals[r][0, val_bytes[r]), pool[0, pool_bytes), the five
+ * input arrays and the workspace, and nothing is written outside out_off[0, n] and out_vals[0, val_bytes). */
+uint64_t seb_dev_get_values_workspace_size(uint64_t n);
+int seb_dev_get_values_plan(const uint8_t *status, const uint8_t *source, const uint8_t *run, const uint64_t *vloc,
+                            const uint32_t *vlen, uint64_t n, const uint8_t *const *vals, const uint64_t *val_bytes,
+                            uint32_t num_runs, const uint8_t *pool, uint64_t pool_bytes, void *workspace,
+                            uint64_t workspace_bytes, seb_values_sizes *sizes, void *stream);
+int seb_dev_get_values_emit(const uint8_t *status, const uint8_t *source, const uint8_t *run, const uint64_t *vloc,
+                            const uint32_t *vlen, uint64_t n, const uint8_t *const *vals, const uint64_t *val_bytes,
+                            uint32_t num_runs, const uint8_t *pool, uint64_t pool_bytes, const seb_values_sizes *sizes,
+                            void *workspace, uint64_t *out_off, uint8_t *out_vals, void *stream);
+
 /* ------------- memtable write side: Put / Delete batches into WAL records, the memtable's runs and the flush input ---- */
 /* What LSM.Put / LSM.Delete do to the log and to the active memtable (lsm/lsm.go:97-137, 203-235, lsm/wal.go:31-65,
  * lsm/memtable.go:34-93), for a batch of n ops applied in order by one writer, with lsm.sequence == S before it.

@@ -17,6 +17,9 @@
 //   seb_blockids.cpp  the host half of the block-id step: located cells into ids of the block pool (no HIP
 //                     dependency; seb_blockids.h); its entry points are in seb_sstable.cpp beside seb_blocks_dedup
 //   seb_blockids.hip  its kernels: the resident map, the miss pairs' table, flags, scan, rank, emit
+//   seb_values.cpp    the host half of the Get path's last step: the found values gathered into one buffer (no HIP
+//                     dependency; seb_values.h); its entry points are in seb_recover.cpp beside the Get path's
+//   seb_values.hip    its kernels: tile sums, scan, offsets, the copy balanced by output bytes
 #pragma once
 #include <hip/hip_runtime.h>
 

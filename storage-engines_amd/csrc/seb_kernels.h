@@ -337,6 +337,31 @@ hipError_t launch_get_join_rows(const uint8_t *mem_status, const uint64_t *mem_v
                                 const uint64_t *sst_vloc, const uint32_t *sst_vlen, uint8_t *status, uint8_t *source,
                                 uint16_t *col, uint64_t *vloc, uint32_t *vlen, hipStream_t s);
 
+// seb_values.hip: the Get path's last step (lsm/sstable.go:276-278, lsm/lsm.go:146-180): the found keys' values
+// gathered back to back in batch order, with an offset array.  The plan lives in a caller-provided workspace: a
+// 128-byte header, the tiles' two sums, then 13 bytes per key that the emit's first kernel leaves for its second.
+constexpr uint32_t kValTile = 1024;       // keys per tile of the sums and of the offsets
+constexpr uint32_t kValCopyGrid = 8192;   // the copy's workgroups (4 KiB of output each) before they stride
+struct ValuesArg {  // device pointers; vals[r] / val_bytes[r] for r < num_runs <= kMemRuns; run nullable (read as 0)
+    const uint8_t *status, *source, *run;
+    const uint64_t *vloc;
+    const uint32_t *vlen;
+    uint64_t n;
+    const uint8_t *vals[kMemRuns];
+    uint64_t val_bytes[kMemRuns];
+    uint32_t num_runs;
+    const uint8_t *pool;
+    uint64_t pool_bytes;
+};
+uint64_t values_ws_bytes(uint64_t n);
+// n >= 1, n < 2^32.  Synchronises the stream; sizes_host = one seb_values_sizes; *bad_host = the lowest invalid
+// carrying key, or ~0 where there is none (with one, the sizes hold n alone).
+hipError_t launch_values_plan(const ValuesArg &a, void *ws, void *sizes_host, uint64_t *bad_host, hipStream_t s);
+// sizes: one seb_values_sizes with n == a.n >= 1; nothing is written unless ws holds the plan that returned it, and
+// nothing past out_off[n] and out_vals[val_bytes) in any case.  No copy is launched where val_bytes == 0.
+hipError_t launch_values_emit(const ValuesArg &a, const void *sizes, void *ws, uint64_t *out_off, uint8_t *out_vals,
+                              hipStream_t s);
+
 // seb_blockids.hip: the block-id step between the locate and the block search (the rules: seb_blockids.h).  The
 // miss path's plan lives in a caller-provided workspace: a 128-byte header, an open-addressing table of the smallest
 // power of two >= 2 * max_uniq slots (pair u64, least cell index u32, rank u32), then the tiles' sums.

@@ -1,12 +1,14 @@
 // seb_recover.cpp — the WAL replay's entry points: the C ABI over its host half (seb_memtable.cpp) and its
 // kernels (seb_replay.hip), and seb_wal_recover, ReadAll + recoverFromWAL on host buffers through a context.
 // Below them the batched memtable lookup's, over the same host file and seb_memget.hip, and seb_memtable_get;
-// beside those the Get path's (seb_getpath.cpp, seb_getpath.hip): the compaction of undecided keys and the row join.
+// beside those the Get path's (seb_getpath.cpp, seb_getpath.hip): the compaction of undecided keys and the row join,
+// and its last step's (seb_values.cpp, seb_values.hip): the found values gathered into one buffer.
 #include <new>
 
 #include "seb_getpath.h"
 #include "seb_host.h"
 #include "seb_memtable.h"
+#include "seb_values.h"
 
 using namespace seb;
 
@@ -407,6 +409,102 @@ extern "C" int seb_dev_get_join_rows(const uint8_t *mem_status, const uint64_t *
     if ((n && (!mem_status || !status)) || (m && (!row || !sst_status))) return compact_rc(-1, 0, nullptr, who);
     HIP_OR_FAIL(launch_get_join_rows(mem_status, mem_vloc, mem_vlen, n, row, m, sst_status, sst_col, sst_vloc, sst_vlen, status,
                                      source, col, vloc, vlen, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+// ------------------------------------------------ Get values: the found values into one dense buffer (lsm/sstable.go:276-278)
+
+static_assert(sizeof(seb_values_sizes) == sizeof(seb::ValuesSizes) && sizeof(seb_values_sizes) == 32, "seb_values_sizes layout");
+static_assert(SEB_MEM_MAX_RUNS == seb::kValuesMaxRuns && SEB_MEM_MAX_RUNS == kMemRuns, "the runs a key may name");
+
+static int values_rc(int rc, uint64_t bad, const seb_values_sizes *sz, const char *who) {
+    switch (rc) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_INVALID, "%s: 2^32 keys or more", who);
+    case -3:
+        return fail(SEB_ERR_INVALID, "%s: key %llu is found but its value does not lie inside the source it names", who,
+                    (unsigned long long)bad);
+    case -4:
+        return fail(SEB_ERR_RANGE, "%s: val_cap is below the values' %llu bytes; retry with *sizes", who,
+                    (unsigned long long)sz->val_bytes);
+    case -5:
+        return fail(SEB_ERR_INVALID, "%s: more than %u runs", who, SEB_MEM_MAX_RUNS);
+    default:
+        return fail(SEB_ERR_INVALID, "%s: a null argument", who);
+    }
+}
+
+extern "C" int seb_get_values(const uint8_t *status, const uint8_t *source, const uint8_t *run, const uint64_t *vloc,
+                              const uint32_t *vlen, uint64_t n, const uint8_t *const *vals, const uint64_t *val_bytes,
+                              uint32_t num_runs, const uint8_t *pool, uint64_t pool_bytes, seb_values_sizes *sizes,
+                              uint64_t *out_off, uint8_t *out_vals, uint64_t val_cap) {
+    uint64_t bad = 0;
+    const int rc = seb::get_values(status, source, run, vloc, vlen, n, ValueSources{vals, val_bytes, num_runs, pool, pool_bytes},
+                                   (seb::ValuesSizes *)sizes, out_off, out_vals, val_cap, &bad);
+    return values_rc(rc, bad, sizes, "seb_get_values");
+}
+
+extern "C" uint64_t seb_dev_get_values_workspace_size(uint64_t n) { return n >= (1ull << 32) ? 0 : values_ws_bytes(n); }
+
+// The argument checks the plan and the emit share; *a is filled where they pass and n != 0.
+static int values_args(const uint8_t *status, const uint8_t *source, const uint8_t *run, const uint64_t *vloc,
+                       const uint32_t *vlen, uint64_t n, const uint8_t *const *vals, const uint64_t *val_bytes, uint32_t num_runs,
+                       const uint8_t *pool, uint64_t pool_bytes, const void *workspace, ValuesArg *a, const char *who) {
+    if (n >= (1ull << 32)) return values_rc(-2, 0, nullptr, who);
+    if (num_runs > SEB_MEM_MAX_RUNS) return values_rc(-5, 0, nullptr, who);
+    if ((num_runs && (!vals || !val_bytes)) || (pool_bytes && !pool)) return values_rc(-1, 0, nullptr, who);
+    if (n == 0) return SEB_OK;
+    if (!status || !source || !vloc || !vlen || !workspace || (num_runs > 1 && !run)) return values_rc(-1, 0, nullptr, who);
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)vloc & 7) || ((uintptr_t)vlen & 3))
+        return fail(SEB_ERR_INVALID, "%s: the workspace is not 16-byte aligned, vloc not 8-byte aligned, or vlen not 4-byte "
+                    "aligned", who);
+    *a = ValuesArg{};
+    a->status = status, a->source = source, a->run = run, a->vloc = vloc, a->vlen = vlen, a->n = n;
+    for (uint32_t r = 0; r < num_runs; ++r) a->vals[r] = vals[r], a->val_bytes[r] = val_bytes[r];
+    a->num_runs = num_runs, a->pool = pool, a->pool_bytes = pool_bytes;
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_get_values_plan(const uint8_t *status, const uint8_t *source, const uint8_t *run, const uint64_t *vloc,
+                                       const uint32_t *vlen, uint64_t n, const uint8_t *const *vals, const uint64_t *val_bytes,
+                                       uint32_t num_runs, const uint8_t *pool, uint64_t pool_bytes, void *workspace,
+                                       uint64_t workspace_bytes, seb_values_sizes *sizes, void *stream) {
+    const char *who = "seb_dev_get_values_plan";
+    enter();
+    if (!sizes) return values_rc(-1, 0, nullptr, who);
+    *sizes = seb_values_sizes{n, 0, 0, 0};
+    ValuesArg a;
+    int rc;
+    if ((rc = values_args(status, source, run, vloc, vlen, n, vals, val_bytes, num_runs, pool, pool_bytes, workspace, &a, who)))
+        return rc;
+    if (n == 0) return SEB_OK;
+    const uint64_t want = values_ws_bytes(n);
+    if (workspace_bytes < want)
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes for %llu keys", who, (unsigned long long)workspace_bytes,
+                    (unsigned long long)want, (unsigned long long)n);
+    uint64_t bad = ~0ull;
+    HIP_OR_FAIL(launch_values_plan(a, workspace, sizes, &bad, (hipStream_t)stream));
+    return bad == ~0ull ? SEB_OK : values_rc(-3, bad, nullptr, who);
+}
+
+extern "C" int seb_dev_get_values_emit(const uint8_t *status, const uint8_t *source, const uint8_t *run, const uint64_t *vloc,
+                                       const uint32_t *vlen, uint64_t n, const uint8_t *const *vals, const uint64_t *val_bytes,
+                                       uint32_t num_runs, const uint8_t *pool, uint64_t pool_bytes, const seb_values_sizes *sizes,
+                                       void *workspace, uint64_t *out_off, uint8_t *out_vals, void *stream) {
+    const char *who = "seb_dev_get_values_emit";
+    enter();
+    if (!sizes) return values_rc(-1, 0, nullptr, who);
+    ValuesArg a;
+    int rc;
+    if ((rc = values_args(status, source, run, vloc, vlen, n, vals, val_bytes, num_runs, pool, pool_bytes, workspace, &a, who)))
+        return rc;
+    if (sizes->n != n || sizes->found > sizes->n) return fail(SEB_ERR_INVALID, "%s: sizes are not this batch's plan", who);
+    if (n == 0) return SEB_OK;
+    if (!out_off || (sizes->val_bytes && !out_vals)) return values_rc(-1, 0, nullptr, who);
+    if ((uintptr_t)out_off & 7) return fail(SEB_ERR_INVALID, "%s: out_off is not 8-byte aligned", who);
+    HIP_OR_FAIL(launch_values_emit(a, sizes, workspace, out_off, out_vals, (hipStream_t)stream));
     return SEB_OK;
 }
 

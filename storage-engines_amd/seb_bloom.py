@@ -87,6 +87,13 @@ class seb_compact_sizes(C.Structure):
         return (self.n, self.undecided, self.key_bytes)
 
 
+class seb_values_sizes(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("found", C.c_uint64), ("val_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.n, self.found, self.val_bytes)
+
+
 class seb_blockids_sizes(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("resident", C.c_uint64), ("misses", C.c_uint64), ("uniq", C.c_uint64),
                 ("bad", C.c_uint64), ("reserved", C.c_uint64)]
@@ -221,6 +228,13 @@ _SIGS = {
     "seb_dev_get_compact_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _u64, C.POINTER(seb_compact_sizes), _vp]),
     "seb_dev_get_compact_emit": (_i, [C.POINTER(seb_keys), _vp, C.POINTER(seb_compact_sizes), _vp, _vp, _vp, _vp, _vp]),
     "seb_dev_get_join_rows": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_get_values": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_u64), _u32, _vp, _u64,
+                            C.POINTER(seb_values_sizes), _vp, _vp, _u64]),
+    "seb_dev_get_values_workspace_size": (_u64, [_u64]),
+    "seb_dev_get_values_plan": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_u64), _u32, _vp, _u64, _vp,
+                                     _u64, C.POINTER(seb_values_sizes), _vp]),
+    "seb_dev_get_values_emit": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_u64), _u32, _vp, _u64,
+                                     C.POINTER(seb_values_sizes), _vp, _vp, _vp, _vp]),
     "seb_memtable_get": (_i, [_vp, C.POINTER(seb_keys), C.POINTER(seb_run), _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_wal_frame_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, C.POINTER(_u64)]),
     "seb_wal_frame_emit": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _u64, _vp, _u64]),
@@ -1598,6 +1612,91 @@ def dev_get_join_rows(mem_status, n: int, row, m: int, sst_status, status, sourc
     check(lib().seb_dev_get_join_rows(_ptr(mem_status), _ptr(mem_vloc), _ptr(mem_vlen), n, _ptr(row), m, _ptr(sst_status),
                                       _ptr(sst_col), _ptr(sst_vloc), _ptr(sst_vlen), _ptr(status), _ptr(source), _ptr(col),
                                       _ptr(vloc), _ptr(vlen), _stream(stream)))
+
+
+# ------------------------------- Get values: the found values into one dense buffer (lsm/sstable.go:276-278)
+
+def get_values(status, source, run, vloc, vlen, vals=(), pool=None, val_cap: int | None = None, val_bytes=None):
+    """The host half and the device form's reference: the values of the keys whose status is GET_FOUND, back to back
+    in batch order.  source 0 reads vals[run[i]] (the runs' value bytes, u8 arrays; None for a null pointer, whose
+    size val_bytes[r] then gives), source 1 reads pool; run may be None with at most one run.  Returns (sizes,
+    out_off u64 n + 1, out_vals u8); sizes = (n, found, val_bytes).  val_cap sizes out_vals instead of a plan: below
+    the values' bytes it raises SebError (RANGE) with `.sizes` set for the retry.  An invalid found key raises
+    SebError (INVALID) naming the lowest one."""
+    st = np.ascontiguousarray(status, dtype=np.uint8)
+    so = np.ascontiguousarray(source, dtype=np.uint8)
+    rn = None if run is None else np.ascontiguousarray(run, dtype=np.uint8)
+    vl = np.ascontiguousarray(vloc, dtype=np.uint64)
+    vn = np.ascontiguousarray(vlen, dtype=np.uint32)
+    n = st.size
+    for name, a in (("source", so), ("run", rn), ("vloc", vl), ("vlen", vn)):
+        if a is not None and a.size != n:
+            raise ValueError(f"{name} holds {a.size} elements, the batch has {n} keys")
+    keep = [None if v is None else np.ascontiguousarray(v, dtype=np.uint8) for v in vals]
+    nr = len(keep)
+    vp = (_vp * max(nr, 1))(*[v.ctypes.data if v is not None else None for v in keep])
+    vb = (_u64 * max(nr, 1))(*(val_bytes if val_bytes is not None else [0 if v is None else v.size for v in keep]))
+    pl = None if pool is None else np.ascontiguousarray(pool, dtype=np.uint8)
+    args = (_np_ptr(st), _np_ptr(so), _np_ptr(rn), _np_ptr(vl), _np_ptr(vn), n, vp if nr else None, vb if nr else None, nr,
+            pl.ctypes.data if pl is not None else None, pl.size if pl is not None else 0)
+    sz = seb_values_sizes()
+    if val_cap is None:
+        check(lib().seb_get_values(*args, C.byref(sz), None, None, 0))
+        val_cap = sz.val_bytes
+    out_off, out_vals = np.zeros(n + 1, np.uint64), np.zeros(max(val_cap, 1), np.uint8)
+    rc = lib().seb_get_values(*args, C.byref(sz), out_off.ctypes.data, out_vals.ctypes.data, val_cap)
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.sizes = sz.as_tuple()
+        raise err
+    return sz.as_tuple(), out_off, out_vals[: sz.val_bytes]
+
+
+def dev_get_values_workspace_size(n: int) -> int:
+    return lib().seb_dev_get_values_workspace_size(n)
+
+
+def _values_dev_args(status, source, run, vloc, vlen, n, vals, val_bytes, pool, pool_bytes):
+    for name, t, size in (("status", status, n), ("source", source, n), ("run", run, n), ("vloc", vloc, 8 * n),
+                          ("vlen", vlen, 4 * n)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {n} keys need {size}")
+    nr = len(vals)
+    if val_bytes is None:
+        val_bytes = [_nbytes(v) if v is not None else 0 for v in vals]
+    vp = (_vp * max(nr, 1))(*[_ptr(v) for v in vals])
+    vb = (_u64 * max(nr, 1))(*val_bytes)
+    if pool_bytes is None:
+        pool_bytes = _nbytes(pool) if pool is not None else 0
+    return (_ptr(status), _ptr(source), _ptr(run), _ptr(vloc), _ptr(vlen), n, vp if nr else None, vb if nr else None, nr,
+            _ptr(pool), pool_bytes)
+
+
+def dev_get_values_plan(status, source, run, vloc, vlen, n: int, vals, pool, ws, val_bytes=None, pool_bytes=None,
+                        ws_bytes: int | None = None, stream=None) -> seb_values_sizes:
+    """Device form: sizes the gather of the found keys' values.  status / source / run (n u8; run None with at most
+    one run), vloc (n u64) and vlen (n u32) as dev_get_join_rows and dev_runs_search wrote them; vals = the runs'
+    value tensors (val_bytes defaults to their sizes; None for a null pointer), pool = the block pool tensor.  The
+    plan goes into the workspace tensor `ws` (dev_get_values_workspace_size(n) bytes, 16-byte aligned).
+    Synchronises; returns the sizes (.n, .found, .val_bytes) that dev_get_values_emit takes; an invalid found key
+    raises SebError (INVALID) naming the lowest one."""
+    args = _values_dev_args(status, source, run, vloc, vlen, n, vals, val_bytes, pool, pool_bytes)
+    sz = seb_values_sizes()
+    check(lib().seb_dev_get_values_plan(*args, _ptr(ws), (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes,
+                                        C.byref(sz), _stream(stream)))
+    return sz
+
+
+def dev_get_values_emit(status, source, run, vloc, vlen, n: int, vals, pool, sizes: seb_values_sizes, ws, out_off, out_vals,
+                        val_bytes=None, pool_bytes=None, stream=None) -> None:
+    """Device form: writes out_off (n + 1 u64) and out_vals (sizes.val_bytes u8, any alignment; None where that is
+    0) from the same inputs and workspace as the plan.  Not synchronised."""
+    for name, t, size in (("out_off", out_off, 8 * (n + 1) if n else 0), ("out_vals", out_vals, sizes.val_bytes),
+                          ("ws", ws, dev_get_values_workspace_size(n) if n else 0)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, the plan needs {size}")
+    args = _values_dev_args(status, source, run, vloc, vlen, n, vals, val_bytes, pool, pool_bytes)
+    check(lib().seb_dev_get_values_emit(*args, C.byref(sizes), _ptr(ws), _ptr(out_off), _ptr(out_vals), _stream(stream)))
 
 
 # ------------------------------- block ids: located cells (slot, block offset) into ids of the block pool
