@@ -118,6 +118,9 @@ int seb_abi_version(void);
  *                     or return the error (0)
  *   "fault_inject"    test only: the Go API mirror's device path fails with SEB_ERR_DEVICE (1) or
  *                     SEB_ERR_INTERNAL (2), or not (0)
+ *   "hidx_hash_mask"  test only: the hash index's key hash is AND-ed with it before the home slot and the tag are
+ *                     taken (0, default: off), so that many keys share both and the key compare and long probe
+ *                     chains are reached; set it before the table's first insert and keep it for its Gets
  * Environment variables SEB_<NAME> (upper case) set the initial values. */
 int seb_set_option(const char *name, int64_t value);
 int seb_get_option(const char *name, int64_t *value);
@@ -1140,6 +1143,115 @@ int seb_dev_wal_crc(uint8_t *data, const uint64_t *rec_off, uint64_t n, int mode
  * SEB_OK if the image ends on a record boundary, SEB_ERR_SHORT if the tail is a truncated header or
  * payload (ReadAll's "failed to read WAL header/data" error), SEB_ERR_INVALID if cap < records + 1. */
 int seb_wal_scan(const uint8_t *data, uint64_t bytes, uint64_t *rec_off, uint64_t cap, uint64_t *n);
+
+/* ------------- hash index, read side: recover() for a set of segment images, Get for a key batch ---- */
+/* The reference's second engine (hashindex/) is a Bitcask-style store: append-only segment files and an in-memory map
+ * from key to (segment, offset, size).  This group is its read side: what recover() (hashindex/recovery.go:14-141)
+ * makes of the segment files, and what Get (hashindex/hashindex.go:217-260 -> segment.read, hashindex/segment.go:
+ * 127-183) answers from them, for a key batch.  The write side (append's framing, segment rotation) and
+ * compactSegments, whose output order is a Go map's, are out of scope.
+ *
+ * Layout: the caller holds the segment images back to back, OLDEST FIRST (ascending segment id), in one byte pool of
+ * pool_bytes < 2^47, with per-segment host arrays seg_base[s] (the image's first byte in the pool) and seg_bytes[s].
+ * A record is named by its POOL OFFSET; because the segments lie in id order, the later record of a key is the one
+ * at the greater pool offset, the only order the device needs.
+ *
+ * The record (segment.go:14-18, 61-125): [crc u32][timestamp u64][keySize u32][valueSize u32][key][value], little-
+ * endian, a SEB_SEG_HEADER_BYTES header, crc = ChecksumIEEE(record[4:]).  valueSize == 0 is a tombstone.
+ *
+ * recover(): the segments in ascending id, each from offset 0.  Where fewer than 20 bytes remain, or the payload
+ * runs past the end of the file, ReadAt returns io.EOF and recover BREAKS WITHOUT TRUNCATING: the segment keeps its
+ * size (short_tail).  A complete record whose CRC does not match CUTS the segment at that record's offset (Truncate,
+ * size = offset): it and everything behind it in this segment is dropped; later segments are still read.  Every
+ * record before that sets latestValues[key]; the last one in (segment, offset) order wins.  A key of length 0 is
+ * accepted here (only Put refuses it).  TOMBSTONES STAY IN THE INDEX: recover's `entry.size == 0` test is never true,
+ * size being the whole record's, so the key count after recovery is the number of distinct keys, deleted ones
+ * included.
+ *
+ * Get: the index lookup, then segment.read, which re-verifies the record's CRC on every read (a mismatch is an
+ * error) and only then looks at the value (an empty one is ErrKeyNotFound).  Per key: SEB_GET_MISS where the key is
+ * absent or its latest record is a tombstone; SEB_GET_ERROR on a CRC mismatch (a corrupted tombstone included: the
+ * CRC comes first); SEB_GET_FOUND with rec = the record's pool offset, vloc = rec + 20 + keySize and vlen =
+ * valueSize.  MISS and ERROR rows get rec = SEB_HIDX_NO_RECORD, vloc = 0, vlen = 0.  With verify == 0 the CRC is not
+ * looked at.  The (status, vloc, vlen) arrays are the ones the LSM Get path ends in, so seb_dev_get_values gathers
+ * the values from them unchanged, with the segment pool as its `pool`, source = 1 and num_runs = 0.
+ *
+ * ONE DEPARTURE from the reference: a header with keySize + valueSize >= 2^32 is treated as a CRC failure: the
+ * segment is cut there.  The reference adds the two as uint32, reads the wrapped length, and then fails the CRC
+ * (with probability 1 - 2^-32) or panics on the slice.  seb_seg_scan lists such a record as its segment's last, and
+ * every verify fails it. */
+#define SEB_SEG_HEADER_BYTES 20u
+#define SEB_HIDX_NO_RECORD UINT64_MAX
+
+/* Host only.  seb_seg_scan: one segment image's sequential header walk, as seb_wal_scan but with the 20-byte header:
+ * rec_off[0, *n) = the records' POOL offsets (base + file offset), *short_tail = 1 iff the image ends inside a header
+ * or a payload (that tail is no record).  The walk trusts every header's sizes and looks at no CRC, so behind a
+ * record that seb_seg_verify fails the offsets and *short_tail describe bytes that recover never reads: they mean
+ * something only for a segment that is not cut (seb_hidx_recover reports short_tail = 0 for a cut one).
+ * SEB_ERR_INVALID: more than cap records (bytes / 20 + 1 always suffice), a
+ * NULL n or short_tail, NULL data with bytes != 0.
+ * seb_seg_verify: records [seg_first[s], seg_first[s + 1]) belong to segment s (seg_first[0] = 0, seg_first[
+ * num_segments] = num_records).  ok[r] (nullable) = record r lies whole inside the pool, passes the 2^32 rule and
+ * its CRC matches; valid[s] = the records of segment s before its first bad one; size_after[s] = the segment's size
+ * after recover: the cut offset, or its unchanged seg_bytes[s]; live[r] (nullable) = 1 iff r < seg_first[s] +
+ * valid[s], the records the index is built from.
+ * seb_hidx_lookup: the whole answer on the host, through a hash map built inside the call from the live records
+ * (live nullable: all of them; one that does not lie inside the pool takes no part); no table layout is exposed.
+ * keys in every seb_keys layout, host memory; rec, vloc, vlen and distinct are nullable; *distinct = the index's key
+ * count.  It is the reference for the device form and what a caller without a GPU uses. */
+int seb_seg_scan(const uint8_t *data, uint64_t bytes, uint64_t base, uint64_t *rec_off, uint64_t cap, uint64_t *n,
+                 int *short_tail);
+int seb_seg_verify(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t num_records,
+                   const uint64_t *seg_first, const uint64_t *seg_base, const uint64_t *seg_bytes, uint64_t num_segments,
+                   uint8_t *ok, uint64_t *valid, uint64_t *size_after, uint8_t *live);
+int seb_hidx_lookup(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                    uint64_t num_records, const seb_keys *keys, int verify, uint8_t *status, uint64_t *rec, uint64_t *vloc,
+                    uint32_t *vlen, uint64_t *distinct);
+
+/* Device pointers (table 16-byte aligned; rec_off, seg_first, valid, rec, vloc and key offsets 8-byte aligned; vlen
+ * 4-byte aligned; the pool, keys, ok, live, status and source at any byte alignment).  Not synchronised unless
+ * stated.  SEB_ERR_INVALID and nothing launched: a NULL required pointer, a misaligned one, pool_bytes >= 2^47,
+ * capacity > 2^40.
+ *
+ * The table is opaque: seb_dev_hidx_table_bytes(capacity) bytes (0 for capacity > 2^40), open addressing with linear
+ * probing over the smallest power of two >= 2 * capacity slots.  seb_dev_hidx_clear empties it.
+ * seb_dev_seg_verify: ok, valid (DEVICE memory here) and live (nullable) as seb_seg_verify gives them; size_after
+ * follows on the host from valid, rec_off and the segments' bases.  Limits: fewer than 2^38 records, 2^32 segments.
+ * seb_dev_hidx_insert: every record with live[r] != 0 (live nullable: all) goes into the table.  A record that does
+ * not lie whole inside the pool is counted as bad and skipped.  The call may be repeated on the same table with
+ * records at greater offsets (the active segment grew and the caller appended to the pool); the result equals one
+ * insert of everything.  The pool must not change while an insert runs.
+ * seb_dev_hidx_count SYNCHRONISES: *distinct = the occupied slots = the index's key count, *bad_records = the
+ * skipped ones (both nullable).  SEB_ERR_RANGE: the table filled during an insert since the last clear (more than
+ * capacity distinct keys); clear and insert again: a capacity of the live records cannot fail that way.
+ * seb_dev_hidx_get: keys in the layouts seb_dev_shard_route takes; status required, rec / vloc / vlen / source
+ * nullable; source[i] = 1 for a FOUND key (the pool holds its value), else 0.  NO INSERT MAY RUN CONCURRENTLY: the
+ * probe reads the table with plain loads.  Bounds, whatever the table or the pool hold: every slot index is masked,
+ * every record is re-checked against pool_bytes before a byte of it is read, the probe is a counted loop of at most
+ * table-size steps, and nothing is written outside the keys->n elements of the five output arrays. */
+uint64_t seb_dev_hidx_table_bytes(uint64_t capacity);
+int seb_dev_hidx_clear(void *table, uint64_t capacity, void *stream);
+int seb_dev_seg_verify(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t num_records,
+                       const uint64_t *seg_first, uint64_t num_segments, uint8_t *ok, uint64_t *valid, uint8_t *live,
+                       void *stream);
+int seb_dev_hidx_insert(void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off,
+                        const uint8_t *live, uint64_t num_records, void *stream);
+int seb_dev_hidx_count(const void *table, uint64_t capacity, uint64_t *distinct, uint64_t *bad_records, void *stream);
+int seb_dev_hidx_get(const void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes, const seb_keys *keys,
+                     int verify, uint8_t *status, uint64_t *rec, uint64_t *vloc, uint32_t *vlen, uint8_t *source,
+                     void *stream);
+
+/* recover() on a context; synchronous.  images[s] / image_bytes[s]: the segment files in HOST memory, oldest first.
+ * dev_pool (DEVICE memory of pool_cap >= the images' total bytes) receives them back to back; dev_table (DEVICE
+ * memory of seb_dev_hidx_table_bytes(capacity) bytes) is cleared and receives the index: scan on the host, upload,
+ * verify, insert.  Host outputs per segment: valid, size_after, short_tail and cut (u8; both nullable); *records
+ * (all scanned), *live_records (the sum of valid) and *distinct (the key count), each nullable.  SEB_ERR_RANGE: pool_cap
+ * below the images' bytes (nothing is done), or the table filled: the per-segment outputs, *records and
+ * *live_records are then filled, and a retry with capacity = *live_records cannot fail that way. */
+int seb_hidx_recover(seb_ctx *ctx, const uint8_t *const *images, const uint64_t *image_bytes, uint64_t num_segments,
+                     uint8_t *dev_pool, uint64_t pool_cap, void *dev_table, uint64_t capacity, uint64_t *valid,
+                     uint64_t *size_after, uint8_t *short_tail, uint8_t *cut, uint64_t *records, uint64_t *live_records,
+                     uint64_t *distinct);
 
 #ifdef __cplusplus
 }

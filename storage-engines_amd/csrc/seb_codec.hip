@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "seb_crc.h"
 #include "seb_device.h"
 #include "seb_kernels.h"
 
@@ -265,48 +266,7 @@ hipError_t launch_route_partition(const KeyBatch &kb, uint32_t bits, uint32_t *p
 }
 
 // ------------------------------------------------------------------ WAL CRC32-IEEE ----------
-// crc32.ChecksumIEEE: reflected polynomial 0xEDB88320, init ~0, final ~ (Go hash/crc32).
-// Slicing-by-4 tables, generated at compile time, staged in LDS per workgroup.
-
-struct CrcTables {
-    uint32_t t[4][256];
-};
-constexpr CrcTables make_crc_tables() {
-    CrcTables c{};
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t v = i;
-        for (int b = 0; b < 8; ++b) v = (v & 1u) ? (v >> 1) ^ 0xEDB88320u : v >> 1;
-        c.t[0][i] = v;
-    }
-    for (uint32_t i = 0; i < 256; ++i)
-        for (int k = 1; k < 4; ++k) c.t[k][i] = (c.t[k - 1][i] >> 8) ^ c.t[0][c.t[k - 1][i] & 0xffu];
-    return c;
-}
-__device__ const CrcTables kCrcTab = make_crc_tables();
-
-__device__ __forceinline__ uint32_t crc_word(uint32_t crc, uint32_t w, const uint32_t (*t)[256]) {
-    const uint32_t x = crc ^ w;
-    return t[3][x & 0xffu] ^ t[2][(x >> 8) & 0xffu] ^ t[1][(x >> 16) & 0xffu] ^ t[0][x >> 24];
-}
-__device__ __forceinline__ uint32_t crc_byte(uint32_t crc, uint32_t b, const uint32_t (*t)[256]) {
-    return (crc >> 8) ^ t[0][(crc ^ b) & 0xffu];
-}
-
-// CRC state over bytes [s, e) of p (raw state in/out: caller applies the ~ at both ends).
-__device__ __forceinline__ uint32_t crc_range(uint32_t crc, const uint8_t *p, uint64_t s, uint64_t e,
-                                              const uint32_t (*t)[256]) {
-    uint64_t a = s;
-    while (a < e && (((uintptr_t)(p + a)) & 3u)) crc = crc_byte(crc, p[a++], t);  // to a dword boundary
-    const uint32_t *w = (const uint32_t *)(p + a);
-    uint64_t nw = (e - a) >> 2;
-    for (uint64_t j = 0; j < nw; ++j) crc = crc_word(crc, w[j], t);
-    for (a += nw << 2; a < e; ++a) crc = crc_byte(crc, p[a], t);
-    return crc;
-}
-
-__device__ __forceinline__ uint32_t ld_u32_le(const uint8_t *p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
+// The tables, crc_word / crc_byte / crc_range and the LDS walk crc_lds: seb_crc.h.
 
 __device__ __forceinline__ void wal_finish(uint8_t *data, uint64_t s, uint64_t len, uint32_t crc, int mode,
                                            uint32_t ks, uint32_t vs, uint32_t stored, uint64_t i,
@@ -339,7 +299,7 @@ __global__ __launch_bounds__(kWalRecs) void k_wal_crc(uint8_t *__restrict__ data
                                                       uint8_t *__restrict__ ok) {
     __shared__ uint32_t tab[4][256];
     __shared__ uint4 stage[kWalLds / 16 + 1];
-    for (uint32_t j = threadIdx.x; j < 1024; j += blockDim.x) (&tab[0][0])[j] = (&kCrcTab.t[0][0])[j];
+    crc_stage_tables(tab);
     const uint64_t r0 = (uint64_t)blockIdx.x * kWalRecs;
     const uint64_t r1 = r0 + kWalRecs < n ? r0 + kWalRecs : n;
     const uintptr_t base = ((uintptr_t)(data + off[r0])) & ~(uintptr_t)15;
@@ -360,20 +320,7 @@ __global__ __launch_bounds__(kWalRecs) void k_wal_crc(uint8_t *__restrict__ data
         const uint8_t *lb = (const uint8_t *)stage;
         const uint32_t b = (uint32_t)((uintptr_t)(data + s) - base);
         if (len >= 4) {
-            const uint32_t *lw = (const uint32_t *)stage;
-            const uint32_t p = b + 4, L = (uint32_t)len - 4, sh = p & 3u;
-            uint32_t wi = p >> 2, cur = lw[wi], c = ~0u;
-            for (uint32_t j = 0; j + 4 <= L; j += 4) {
-                const uint32_t nxt = lw[++wi];
-                c = crc_word(c, __builtin_amdgcn_alignbyte(nxt, cur, sh), tab);
-                cur = nxt;
-            }
-            const uint32_t r = L & 3u;
-            if (r) {
-                const uint32_t w = __builtin_amdgcn_alignbyte(lw[wi + 1], cur, sh);
-                for (uint32_t j = 0; j < r; ++j) c = crc_byte(c, (w >> (8 * j)) & 0xffu, tab);
-            }
-            crc = ~c;
+            crc = crc_lds((const uint32_t *)stage, b + 4, (uint32_t)len - 4, tab);
             stored = (uint32_t)lb[b] | ((uint32_t)lb[b + 1] << 8) | ((uint32_t)lb[b + 2] << 16) |
                      ((uint32_t)lb[b + 3] << 24);
         }

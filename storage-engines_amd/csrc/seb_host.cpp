@@ -96,6 +96,7 @@ static const OptionDesc kOptions[] = {
     SEB_OPT(varlen_tail, 0, 3),
     SEB_OPT(cpu_fallback, 0, 1),
     SEB_OPT(fault_inject, 0, 2),
+    SEB_OPT(hidx_hash_mask, 0, INT64_MAX),
 };
 #undef SEB_OPT
 

@@ -20,6 +20,10 @@
 //   seb_values.cpp    the host half of the Get path's last step: the found values gathered into one buffer (no HIP
 //                     dependency; seb_values.h); its entry points are in seb_recover.cpp beside the Get path's
 //   seb_values.hip    its kernels: tile sums, scan, offsets, the copy balanced by output bytes
+//   seb_hashindex.cpp the host half of the hash index's read side: segment scan, verify and cuts, Get (no HIP
+//                     dependency; seb_hashindex.h)
+//   seb_hashindex.hip its kernels: segment CRC, live flags, table insert, Get (the CRC itself: seb_crc.h)
+//   seb_hidx.cpp      the hash index's entry points and seb_hidx_recover
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -234,6 +238,7 @@ struct seb_ctx {
     seb::DevBuf mg_runs, mg_out;  // seb_memtable_get: the runs' arrays and indexes, a chunk's six output arrays
     seb::DevBuf mw_in, mw_img, mw_ws, mw_out, mw_runs;  // seb_memtable_apply / _fold: the ops + rec_off + delta, the image,
                                                          // the plan's workspace, the run's six arrays, the runs + indexes
+    seb::DevBuf hx_ws;  // seb_hidx_recover: rec_off + seg_first + valid + ok + live
     seb::PinBuf hkeys, hbits;  // small filter builds: keys in, bits out, read and written by the kernels
     uint64_t chunk_bytes = 64ull << 20;
     std::vector<uint64_t> off_tmp[2];

@@ -386,6 +386,25 @@ hipError_t launch_blockids_emit(const uint16_t *cand, const uint64_t *blocks, ui
                                 const void *sizes, const void *ws, uint32_t *bid, uint16_t *uniq_slot, uint64_t *uniq_block,
                                 hipStream_t s);
 
+// seb_hashindex.hip: the hash index's read side (the semantics: seb_hashindex.h).  The table: a 64-byte header
+// [overflow][occupied slots][bad records] and hidx_slots(capacity) slots of one u64 (0 empty, else a hash tag in the
+// high 16 bits and record offset + 1 in the low 48).  hash_mask: the test-only option (0 = off).
+uint64_t hidx_slots(uint64_t capacity);  // the smallest power of two >= 2 * capacity
+uint64_t hidx_table_bytes(uint64_t capacity);
+hipError_t launch_hidx_clear(void *table, uint64_t capacity, hipStream_t s);
+// ok[n], valid[nseg] (device) and live[n] (nullable) from rec_off[n] and seg_first[nseg + 1] (device).
+hipError_t launch_seg_verify(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t n,
+                             const uint64_t *seg_first, uint64_t nseg, uint8_t *ok, uint64_t *valid, uint8_t *live,
+                             hipStream_t s);
+hipError_t launch_hidx_insert(void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes,
+                              const uint64_t *rec_off, const uint8_t *live, uint64_t n, uint64_t hash_mask, hipStream_t s);
+// Synchronises the stream; state_host = the header's three words.
+hipError_t launch_hidx_state(const void *table, uint64_t state_host[3], hipStream_t s);
+// rec, vloc, vlen and source are nullable; nothing outside the kb.n elements of each is written.
+hipError_t launch_hidx_get(const void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes, const KeyBatch &kb,
+                           bool verify, uint64_t hash_mask, uint8_t *status, uint64_t *rec, uint64_t *vloc, uint32_t *vlen,
+                           uint8_t *source, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).
@@ -416,6 +435,8 @@ struct Options {
     int cpu_fallback = 1;         // Go API mirror: a build/probe whose device path fails (SEB_ERR_DEVICE/NOMEM)
                                   // is done on the filter's host copy instead (seb_fallback_count)
     int fault_inject = 0;         // test only: the Go API mirror's device path fails with SEB_ERR_DEVICE
+    uint64_t hidx_hash_mask = 0;  // test only: the hash index's key hash is AND-ed with it (0 = off), so that many
+                                  // keys share a home slot and a tag
 };
 Options &options();
 

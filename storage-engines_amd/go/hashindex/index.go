@@ -1,0 +1,226 @@
+// The read side of the hash index, over the hash index group of libseb_bloom (include/seb_bloom.h): what
+// recover() (hashindex/recovery.go) makes of the segment files, and what Get (hashindex/hashindex.go:217-260 ->
+// segment.read) answers from them, for a key batch.
+//
+//	Recover   the segment files (oldest first) into a device pool and a device key table: scan on the host, upload,
+//	          CRC pass with the cuts, insert (seb_hidx_recover); per segment the valid records, the size after
+//	          recovery, whether it was cut and whether it ends in a short tail; the key count, tombstones included
+//	LookupHost the whole answer on the host, for a caller without a GPU (seb_seg_scan, seb_seg_verify, seb_hidx_lookup)
+//	DevGet    status / rec / vloc / vlen / source for a device key batch (seb_dev_hidx_get); the three arrays the LSM
+//	          Get path ends in, so lsm.DevValuesPlan / DevValuesEmit gather the values from them with the segment
+//	          pool as their pool
+//	DevInsert records appended to the active segment into the same table (seb_dev_seg_verify, seb_dev_hidx_insert,
+//	          seb_dev_hidx_count)
+//
+// One stated departure: a header with keySize + valueSize >= 2^32 counts as a CRC failure and cuts its segment; the
+// reference adds the two as uint32 and then fails the CRC or panics on the slice.  The write side (append's framing,
+// segment rotation) and compactSegments are not here.
+//
+// Not compiled in this repository's pipeline (no Go toolchain in the image); the C ABI it calls is tested through
+// the Python binding (tests/test_hashindex.py, tests/test_gpu_hashindex.py).
+package hashindex
+
+/*
+#include <stdint.h>
+#include <stdlib.h>
+#include "seb_bloom.h"
+*/
+import "C"
+
+import (
+	"fmt"
+	"unsafe"
+)
+
+// Get statuses (seb_get_status).
+const (
+	GetMiss  = 0
+	GetFound = 1
+	GetError = 2 // the record's CRC does not match
+)
+
+// NoRecord is rec for a key that is not found.
+const NoRecord = ^uint64(0)
+
+func bytesPtr(b []byte) *C.uint8_t {
+	if len(b) == 0 {
+		return nil
+	}
+	return (*C.uint8_t)(unsafe.Pointer(&b[0]))
+}
+
+func u64Ptr(v []uint64) *C.uint64_t {
+	if len(v) == 0 {
+		return nil
+	}
+	return (*C.uint64_t)(unsafe.Pointer(&v[0]))
+}
+
+func lastError(what string) error {
+	return fmt.Errorf("%s: %s", what, C.GoString(C.seb_last_error()))
+}
+
+// TableBytes is the device memory a table of `capacity` keys needs (16-byte aligned).
+func TableBytes(capacity uint64) uint64 { return uint64(C.seb_dev_hidx_table_bytes(C.uint64_t(capacity))) }
+
+// Recovered is what recover() leaves per segment, and the index's size.
+type Recovered struct {
+	Valid, SizeAfter []uint64
+	ShortTail, Cut   []bool
+	Records          uint64 // scanned
+	LiveRecords      uint64 // the sum of Valid
+	Keys             uint64 // distinct keys, tombstones included (HashIndex.Count after recovery)
+}
+
+// ErrTableFull is returned with Recovered filled (but for Keys): retry with capacity = LiveRecords.
+var ErrTableFull = fmt.Errorf("the key table filled")
+
+// Recover runs recover() for the segment files (host bytes, oldest first) on ctx (a seb_ctx): devPool (device
+// memory of poolCap bytes, at least the files' total) receives them back to back, devTable (TableBytes(capacity)
+// bytes of device memory) the index.
+func Recover(ctx unsafe.Pointer, segments [][]byte, devPool unsafe.Pointer, poolCap uint64, devTable unsafe.Pointer, capacity uint64) (*Recovered, error) {
+	s := len(segments)
+	// the images' pointers live in C memory for the call (cgo forbids Go pointers to Go pointers)
+	ptrs := (**C.uint8_t)(C.calloc(C.size_t(s+1), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	defer C.free(unsafe.Pointer(ptrs))
+	pv := unsafe.Slice(ptrs, s+1)
+	sizes := make([]uint64, s+1)
+	for i, seg := range segments {
+		pv[i], sizes[i] = bytesPtr(seg), uint64(len(seg))
+	}
+	r := &Recovered{Valid: make([]uint64, s), SizeAfter: make([]uint64, s), ShortTail: make([]bool, s), Cut: make([]bool, s)}
+	tail, cut := make([]byte, s+1), make([]byte, s+1)
+	var records, live, keys C.uint64_t
+	rc := C.seb_hidx_recover((*C.seb_ctx)(ctx), ptrs, u64Ptr(sizes), C.uint64_t(s), (*C.uint8_t)(devPool), C.uint64_t(poolCap),
+		devTable, C.uint64_t(capacity), u64Ptr(r.Valid), u64Ptr(r.SizeAfter), bytesPtr(tail), bytesPtr(cut), &records, &live, &keys)
+	for i := 0; i < s; i++ {
+		r.ShortTail[i], r.Cut[i] = tail[i] != 0, cut[i] != 0
+	}
+	r.Records, r.LiveRecords, r.Keys = uint64(records), uint64(live), uint64(keys)
+	if rc == C.SEB_ERR_RANGE && r.LiveRecords > capacity {
+		return r, ErrTableFull
+	}
+	if rc != 0 {
+		return nil, lastError("failed to recover the hash index")
+	}
+	return r, nil
+}
+
+// Answer is one key's Get: Status, the record's pool offset, and where its value lies in the pool.
+type Answer struct {
+	Status byte
+	Rec    uint64
+	VLoc   uint64
+	VLen   uint32
+}
+
+// LookupHost is recover() and Get on the host: the segments are scanned and verified, the index is a map built
+// inside the call.  keys in the variable-length layout: key i = keyData[keyOff[i]:keyOff[i+1]].
+func LookupHost(segments [][]byte, keyData []byte, keyOff []uint64, verify bool) ([]Answer, *Recovered, error) {
+	s := len(segments)
+	var pool []byte
+	var recOff []uint64
+	first, base, size := make([]uint64, s+1), make([]uint64, s+1), make([]uint64, s+1)
+	r := &Recovered{Valid: make([]uint64, s), SizeAfter: make([]uint64, s), ShortTail: make([]bool, s), Cut: make([]bool, s)}
+	for i, seg := range segments {
+		off := make([]uint64, len(seg)/int(C.SEB_SEG_HEADER_BYTES)+1)
+		var n C.uint64_t
+		var tail C.int
+		if C.seb_seg_scan(bytesPtr(seg), C.uint64_t(len(seg)), C.uint64_t(len(pool)), u64Ptr(off), C.uint64_t(len(off)), &n, &tail) != 0 {
+			return nil, nil, lastError("failed to scan a segment")
+		}
+		first[i], base[i], size[i] = uint64(len(recOff)), uint64(len(pool)), uint64(len(seg))
+		r.ShortTail[i] = tail != 0
+		recOff = append(recOff, off[:n]...)
+		pool = append(pool, seg...)
+	}
+	first[s] = uint64(len(recOff))
+	live := make([]byte, len(recOff)+1)
+	if C.seb_seg_verify(bytesPtr(pool), C.uint64_t(len(pool)), u64Ptr(recOff), C.uint64_t(len(recOff)), u64Ptr(first), u64Ptr(base),
+		u64Ptr(size), C.uint64_t(s), nil, u64Ptr(r.Valid), u64Ptr(r.SizeAfter), bytesPtr(live)) != 0 {
+		return nil, nil, lastError("failed to verify the segments")
+	}
+	for i := 0; i < s; i++ {
+		r.Cut[i] = r.Valid[i] < first[i+1]-first[i]
+		r.ShortTail[i] = r.ShortTail[i] && !r.Cut[i]
+		r.LiveRecords += r.Valid[i]
+	}
+	r.Records = uint64(len(recOff))
+	n := len(keyOff) - 1
+	if n < 0 {
+		n = 0
+	}
+	status := make([]byte, n+1)
+	rec, vloc := make([]uint64, n+1), make([]uint64, n+1)
+	vlen := make([]uint32, n+1)
+	kb := C.seb_keys{data: bytesPtr(keyData), offsets: u64Ptr(keyOff), n: C.uint64_t(n)}
+	v := C.int(0)
+	if verify {
+		v = 1
+	}
+	var keys C.uint64_t
+	if C.seb_hidx_lookup(bytesPtr(pool), C.uint64_t(len(pool)), u64Ptr(recOff), bytesPtr(live), C.uint64_t(len(recOff)), &kb, v,
+		bytesPtr(status), u64Ptr(rec), u64Ptr(vloc), (*C.uint32_t)(unsafe.Pointer(&vlen[0])), &keys) != 0 {
+		return nil, nil, lastError("failed to look the keys up")
+	}
+	r.Keys = uint64(keys)
+	out := make([]Answer, n)
+	for i := range out {
+		out[i] = Answer{Status: status[i], Rec: rec[i], VLoc: vloc[i], VLen: vlen[i]}
+	}
+	return out, r, nil
+}
+
+// DevKeys is a key batch in device memory, in the layouts seb_dev_shard_route takes.
+type DevKeys struct {
+	Data, Offsets unsafe.Pointer // Offsets nil: fixed-length keys of Stride bytes
+	N             uint64
+	Stride        uint32
+}
+
+// DevGet enqueues Get for a device key batch on `stream`; not synchronised.  status is required; rec, vloc, vlen and
+// source may be nil.  No DevInsert may run concurrently on the same table.
+func DevGet(table unsafe.Pointer, capacity uint64, pool unsafe.Pointer, poolBytes uint64, keys DevKeys, verify bool,
+	status, rec, vloc, vlen, source, stream unsafe.Pointer) error {
+	kb := C.seb_keys{data: (*C.uint8_t)(keys.Data), offsets: (*C.uint64_t)(keys.Offsets), n: C.uint64_t(keys.N), stride: C.uint32_t(keys.Stride)}
+	v := C.int(0)
+	if verify {
+		v = 1
+	}
+	if C.seb_dev_hidx_get(table, C.uint64_t(capacity), (*C.uint8_t)(pool), C.uint64_t(poolBytes), &kb, v, (*C.uint8_t)(status),
+		(*C.uint64_t)(rec), (*C.uint64_t)(vloc), (*C.uint32_t)(vlen), (*C.uint8_t)(source), stream) != 0 {
+		return lastError("failed to get from the hash index")
+	}
+	return nil
+}
+
+// DevInsert verifies n appended records (recOff: their pool offsets in device memory, all of one segment; ok, live:
+// n device bytes each; valid: one device u64) and inserts the live ones; it synchronises and returns the key count.
+// The pool must already hold the records' bytes.  ErrTableFull: clear a larger table and insert everything again.
+func DevInsert(table unsafe.Pointer, capacity uint64, pool unsafe.Pointer, poolBytes uint64, recOff unsafe.Pointer, n uint64,
+	segFirst, ok, live, valid, stream unsafe.Pointer) (uint64, error) {
+	if C.seb_dev_seg_verify((*C.uint8_t)(pool), C.uint64_t(poolBytes), (*C.uint64_t)(recOff), C.uint64_t(n), (*C.uint64_t)(segFirst), 1,
+		(*C.uint8_t)(ok), (*C.uint64_t)(valid), (*C.uint8_t)(live), stream) != 0 {
+		return 0, lastError("failed to verify the appended records")
+	}
+	if C.seb_dev_hidx_insert(table, C.uint64_t(capacity), (*C.uint8_t)(pool), C.uint64_t(poolBytes), (*C.uint64_t)(recOff),
+		(*C.uint8_t)(live), C.uint64_t(n), stream) != 0 {
+		return 0, lastError("failed to insert into the hash index")
+	}
+	var keys C.uint64_t
+	switch C.seb_dev_hidx_count(table, C.uint64_t(capacity), &keys, nil, stream) {
+	case 0:
+		return uint64(keys), nil
+	case C.SEB_ERR_RANGE:
+		return 0, ErrTableFull
+	}
+	return 0, lastError("failed to count the hash index")
+}
+
+// DevClear empties a table; not synchronised.
+func DevClear(table unsafe.Pointer, capacity uint64, stream unsafe.Pointer) error {
+	if C.seb_dev_hidx_clear(table, C.uint64_t(capacity), stream) != 0 {
+		return lastError("failed to clear the hash index")
+	}
+	return nil
+}

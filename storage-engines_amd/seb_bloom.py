@@ -263,6 +263,17 @@ _SIGS = {
     "seb_dev_shard_partition": (_i, [C.POINTER(seb_keys), _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "seb_dev_wal_crc": (_i, [_vp, _vp, _u64, _i, _vp, _vp, _vp]),
     "seb_wal_scan": (_i, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "seb_seg_scan": (_i, [_vp, _u64, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_i)]),
+    "seb_seg_verify": (_i, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "seb_hidx_lookup": (_i, [_vp, _u64, _vp, _vp, _u64, C.POINTER(seb_keys), _i, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "seb_dev_hidx_table_bytes": (_u64, [_u64]),
+    "seb_dev_hidx_clear": (_i, [_vp, _u64, _vp]),
+    "seb_dev_seg_verify": (_i, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "seb_dev_hidx_insert": (_i, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "seb_dev_hidx_count": (_i, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "seb_dev_hidx_get": (_i, [_vp, _u64, _vp, _u64, C.POINTER(seb_keys), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_hidx_recover": (_i, [_vp, C.POINTER(_vp), C.POINTER(_u64), _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp,
+                              C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "seb_dev_pack_residues": (_i, [C.POINTER(seb_keys), _u64, _u32, _vp, _vp]),
     "seb_dev_probe_packed": (_i, [_vp, _u64, _vp, _u64, _u32, _vp, _vp]),
     "seb_dev_probe_emit_packed": (_i, [C.POINTER(seb_keys), _vp, _u64, _u32, _vp, _vp, _vp]),
@@ -1980,3 +1991,260 @@ def wal_scan(image: bytes | np.ndarray) -> tuple[np.ndarray, int]:
     if rc not in (0, -5):
         check(rc)
     return off[: n.value + 1].copy(), rc
+
+
+# ------------------------------- hash index, read side: recover() of segment images, Get of a key batch (hashindex/)
+
+SEG_HEADER_BYTES = 20        # SEB_SEG_HEADER_BYTES
+HIDX_NO_RECORD = 2**64 - 1   # SEB_HIDX_NO_RECORD
+
+
+def _bytes_arg(b) -> np.ndarray:
+    if isinstance(b, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(b), np.uint8)
+    return np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+
+
+def seg_scan(image, base: int = 0, cap: int | None = None) -> tuple[np.ndarray, int]:
+    """One segment image's header walk on the host (hashindex/recovery.go:86-112 without the CRC): (the records' pool
+    offsets base + file offset, short_tail).  cap: the offsets' capacity (default: always enough)."""
+    buf = _bytes_arg(image)
+    cap = buf.size // SEG_HEADER_BYTES + 1 if cap is None else cap
+    off = np.zeros(max(cap, 1), np.uint64)
+    n, tail = _u64(0), _i(0)
+    check(lib().seb_seg_scan(_np_ptr(buf), buf.size, base, off.ctypes.data, cap, C.byref(n), C.byref(tail)))
+    return off[: n.value].copy(), tail.value
+
+
+def segs_scan(segments):
+    """The layout the hash index calls take, from the segment images oldest first: (pool u8, rec_off u64, seg_first
+    u64 S + 1, seg_base u64, seg_bytes u64, short_tail u8)."""
+    imgs = [_bytes_arg(s) for s in segments]
+    seg_bytes = np.array([a.size for a in imgs], np.uint64)
+    seg_base = np.zeros(len(imgs), np.uint64)
+    if len(imgs) > 1:
+        np.cumsum(seg_bytes[:-1], out=seg_base[1:])
+    offs, tails, first = [], [], [0]
+    for a, b in zip(imgs, seg_base):
+        o, t = seg_scan(a, int(b))
+        offs.append(o), tails.append(t), first.append(first[-1] + o.size)
+    pool = np.concatenate(imgs) if imgs else np.zeros(0, np.uint8)
+    rec_off = np.concatenate(offs) if offs else np.zeros(0, np.uint64)
+    return pool, rec_off.astype(np.uint64), np.array(first, np.uint64), seg_base, seg_bytes, np.array(tails, np.uint8)
+
+
+def seg_verify(pool, rec_off, seg_first, seg_base, seg_bytes):
+    """recover()'s CRC pass and cuts on the host: (ok u8 per record, valid u64 and size_after u64 per segment, live u8
+    per record)."""
+    pool, rec_off = _bytes_arg(pool), np.ascontiguousarray(rec_off, dtype=np.uint64)
+    first, base, size = (np.ascontiguousarray(a, dtype=np.uint64) for a in (seg_first, seg_base, seg_bytes))
+    n, s = rec_off.size, first.size - 1
+    ok, live = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    valid, after = np.zeros(s, np.uint64), np.zeros(s, np.uint64)
+    check(lib().seb_seg_verify(_np_ptr(pool), pool.size, _np_ptr(rec_off), n, first.ctypes.data, _np_ptr(base), _np_ptr(size), s,
+                               _np_ptr(ok), _np_ptr(valid), _np_ptr(after), _np_ptr(live)))
+    return ok, valid, after, live
+
+
+def hidx_lookup(pool, rec_off, live, keys, verify: bool = True):
+    """HashIndex.Get for a key batch on the host, over the live records: (status u8, rec u64, vloc u64, vlen u32,
+    distinct).  The reference for dev_hidx_get."""
+    pool, rec_off = _bytes_arg(pool), np.ascontiguousarray(rec_off, dtype=np.uint64)
+    lv = None if live is None else np.ascontiguousarray(live, dtype=np.uint8)
+    kb = as_keys(keys)
+    n = kb.n
+    status, rec = np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+    vloc, vlen = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    distinct = _u64(0)
+    check(lib().seb_hidx_lookup(_np_ptr(pool), pool.size, _np_ptr(rec_off), _np_ptr(lv), rec_off.size, kb.ref, int(bool(verify)),
+                                _np_ptr(status), _np_ptr(rec), _np_ptr(vloc), _np_ptr(vlen), C.byref(distinct)))
+    return status, rec, vloc, vlen, distinct.value
+
+
+def dev_hidx_table_bytes(capacity: int) -> int:
+    return lib().seb_dev_hidx_table_bytes(capacity)
+
+
+def dev_hidx_clear(table, capacity: int, stream=None) -> None:
+    check(lib().seb_dev_hidx_clear(_ptr(table), capacity, _stream(stream)))
+
+
+def dev_seg_verify(pool, pool_bytes: int, rec_off, n: int, seg_first, num_segments: int, ok, valid, live=None,
+                   stream=None) -> None:
+    """Device form of seg_verify: ok (n u8), valid (num_segments u64, device) and live (n u8, optional) from rec_off
+    (n u64) and seg_first (num_segments + 1 u64).  Not synchronised."""
+    check(lib().seb_dev_seg_verify(_ptr(pool), pool_bytes, _ptr(rec_off), n, _ptr(seg_first), num_segments, _ptr(ok),
+                                   _ptr(valid), _ptr(live), _stream(stream)))
+
+
+def dev_hidx_insert(table, capacity: int, pool, pool_bytes: int, rec_off, live, n: int, stream=None) -> None:
+    """The live records (live None: all) into the table.  Not synchronised; dev_hidx_count reports a table that
+    filled."""
+    check(lib().seb_dev_hidx_insert(_ptr(table), capacity, _ptr(pool), pool_bytes, _ptr(rec_off), _ptr(live), n,
+                                    _stream(stream)))
+
+
+def dev_hidx_count(table, capacity: int, stream=None) -> tuple[int, int]:
+    """Synchronises: (distinct keys, bad records skipped); SebError (RANGE) where the table filled."""
+    distinct, bad = _u64(0), _u64(0)
+    check(lib().seb_dev_hidx_count(_ptr(table), capacity, C.byref(distinct), C.byref(bad), _stream(stream)))
+    return distinct.value, bad.value
+
+
+def dev_hidx_get(table, capacity: int, pool, pool_bytes: int, keys: seb_keys, verify: bool, status, rec=None, vloc=None,
+                 vlen=None, source=None, stream=None) -> None:
+    """HashIndex.Get for a device key batch: status (u8), rec / vloc (u64), vlen (u32), source (u8), each of keys.n
+    elements; all but status optional.  No insert may run concurrently.  Not synchronised."""
+    check(lib().seb_dev_hidx_get(_ptr(table), capacity, _ptr(pool), pool_bytes, C.byref(keys), int(bool(verify)), _ptr(status),
+                                 _ptr(rec), _ptr(vloc), _ptr(vlen), _ptr(source), _stream(stream)))
+
+
+def _ctx_hidx_recover(self, segments, dev_pool, dev_table, capacity: int, pool_cap: int | None = None):
+    """seb_hidx_recover: the segment images (host, oldest first) into the device pool and table.  Returns a dict:
+    valid, size_after, short_tail, cut (per segment), records, live_records, distinct.  SebError (RANGE) carries the
+    same dict without `distinct` as `.recovered` where the table filled."""
+    imgs = [_bytes_arg(s) for s in segments]
+    s = len(imgs)
+    ptrs = (_vp * max(s, 1))(*[a.ctypes.data if a.size else None for a in imgs])
+    sizes = (_u64 * max(s, 1))(*[a.size for a in imgs])
+    valid, after = np.zeros(s, np.uint64), np.zeros(s, np.uint64)
+    tail, cut = np.zeros(s, np.uint8), np.zeros(s, np.uint8)
+    records, alive, distinct = _u64(0), _u64(0), _u64(0)
+    cap = (dev_pool.numel() if dev_pool is not None else 0) if pool_cap is None else pool_cap
+    rc = lib().seb_hidx_recover(self._p, ptrs if s else None, sizes if s else None, s, _ptr(dev_pool), cap, _ptr(dev_table),
+                                capacity, _np_ptr(valid), _np_ptr(after), _np_ptr(tail), _np_ptr(cut), C.byref(records),
+                                C.byref(alive), C.byref(distinct))
+    out = dict(valid=valid, size_after=after, short_tail=tail, cut=cut, records=records.value, live_records=alive.value)
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.recovered = out
+        raise err
+    out["distinct"] = distinct.value
+    return out
+
+
+Ctx.hidx_recover = _ctx_hidx_recover
+
+
+class HashIndex:
+    """The read side of the reference's hash index on one device: the segment pool and the key table live in device
+    memory.  recover(segments) is hashindex's recover(); get_batch(keys) is HashIndex.Get for a batch, ending in the
+    values gather (dev_get_values_*) with the segment pool as its pool; insert(tail) takes records appended to the
+    active (last) segment."""
+
+    def __init__(self, device: int = 0):
+        self._ctx = Ctx(device)
+        self.device = device
+        self.pool = self.table = None
+        self.pool_bytes = self.capacity = self.count = 0
+        self.segment_sizes = np.zeros(0, np.uint64)
+        self._images, self._runs = None, []  # the recovered images and every insert's (rec_off, live, n) device tensors:
+                                             # what a rebuild into a larger table needs
+
+    def close(self):
+        self._ctx.close()
+        self.pool = self.table = None
+        self._runs = []
+
+    def recover(self, segments, slack_bytes: int = 0, capacity: int | None = None) -> dict:
+        """The segment images (bytes or u8 arrays, oldest first).  slack_bytes: room kept behind the pool for
+        insert().  Returns Ctx.hidx_recover's dict; `count` and `segment_sizes` (size_after) are set from it."""
+        import torch
+        imgs = [_bytes_arg(s) for s in segments]
+        total = sum(a.size for a in imgs)
+        dev = torch.device("cuda", self.device)
+        self.pool = torch.zeros(max(total + slack_bytes, 16), dtype=torch.uint8, device=dev)
+        self.pool_bytes = total
+        cap = max(total // 64, 16) if capacity is None else capacity
+        while True:
+            self.capacity = cap
+            self.table = torch.empty(dev_hidx_table_bytes(cap), dtype=torch.uint8, device=dev)
+            try:
+                got = self._ctx.hidx_recover(imgs, self.pool, self.table, cap, pool_cap=self.pool.numel())
+                break
+            except SebError as e:
+                if e.code != -4 or not hasattr(e, "recovered") or e.recovered["live_records"] <= cap:
+                    raise
+                cap = e.recovered["live_records"]  # cannot fill again
+        self.count = got["distinct"]
+        self.segment_sizes = got["size_after"].copy()
+        self._images, self._runs = imgs, []  # a rebuild into a larger table scans and verifies them again (_insert_all)
+        return got
+
+    def _insert_all(self):
+        import torch
+        if self._images is not None:  # the recovered segments' records, as the device arrays an insert takes
+            dev = self.pool.device
+            pool, rec_off, first, base, size, _ = segs_scan(self._images)
+            live = seg_verify(pool, rec_off, first, base, size)[3]
+            self._runs.insert(0, (torch.from_numpy(rec_off.view(np.int64).copy()).to(dev), torch.from_numpy(live.copy()).to(dev),
+                                  rec_off.size))
+            self._images = None
+        dev_hidx_clear(self.table, self.capacity)
+        for rec_off, live, n in self._runs:
+            if n:
+                dev_hidx_insert(self.table, self.capacity, self.pool, self.pool_bytes, rec_off, live, n)
+        return dev_hidx_count(self.table, self.capacity)[0]
+
+    def insert(self, tail) -> int:
+        """Records appended to the active segment: `tail` is the bytes written behind it (whole records; a bad one
+        cuts the tail there, as recover would).  Returns the number of records that went in."""
+        import torch
+        buf = _bytes_arg(tail)
+        if self.pool is None or self.pool_bytes + buf.size > self.pool.numel():
+            raise ValueError("the pool has no room for the tail: recover with slack_bytes")
+        dev = self.pool.device
+        rec_off, _ = seg_scan(buf, self.pool_bytes)
+        n = rec_off.size
+        self.pool[self.pool_bytes: self.pool_bytes + buf.size] = torch.from_numpy(buf.copy()).to(dev)
+        self.pool_bytes += buf.size
+        if n == 0:
+            return 0
+        d_off = torch.from_numpy(rec_off.view(np.int64).copy()).to(dev)
+        d_first = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        ok = torch.empty(n, dtype=torch.uint8, device=dev)
+        live = torch.empty(n, dtype=torch.uint8, device=dev)
+        valid = torch.empty(1, dtype=torch.int64, device=dev)
+        dev_seg_verify(self.pool, self.pool_bytes, d_off, n, d_first, 1, ok, valid, live)
+        self._runs.append((d_off, live, n))
+        dev_hidx_insert(self.table, self.capacity, self.pool, self.pool_bytes, d_off, live, n)
+        try:
+            self.count = dev_hidx_count(self.table, self.capacity)[0]
+        except SebError as e:
+            if e.code != -4:
+                raise
+            self.capacity = max(2 * self.capacity, self.count + n)
+            self.table = torch.empty(dev_hidx_table_bytes(self.capacity), dtype=torch.uint8, device=dev)
+            self.count = self._insert_all()
+        took = int(valid.cpu()[0])
+        if len(self.segment_sizes):
+            self.segment_sizes[-1] += np.uint64(buf.size if took == n else int(rec_off[took]) - int(rec_off[0]))
+        return took
+
+    def get_batch(self, keys, verify: bool = True):
+        """HashIndex.Get for a key batch (anything as_keys takes): (status u8, out_off u64 n + 1, out_vals u8): key
+        i's value is out_vals[out_off[i]: out_off[i + 1]] where status[i] == GET_FOUND; GET_ERROR is a CRC mismatch."""
+        import torch
+        kb = as_keys(keys)
+        n = kb.n
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint8)
+        dev = self.pool.device
+        data = torch.from_numpy(kb.data.reshape(-1).copy() if kb.data.size else np.zeros(1, np.uint8)).to(dev)
+        if kb.offsets is not None:
+            dk = dev_keys(data, torch.from_numpy(kb.offsets.view(np.int64).copy()).to(dev))
+        else:
+            dk = dev_keys(data, n=n, stride=kb.stride)
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+        source = torch.empty(n, dtype=torch.uint8, device=dev)
+        vloc = torch.empty(n, dtype=torch.int64, device=dev)
+        vlen = torch.empty(n, dtype=torch.int32, device=dev)
+        dev_hidx_get(self.table, self.capacity, self.pool, self.pool_bytes, dk, verify, status, None, vloc, vlen, source)
+        ws = torch.empty(dev_get_values_workspace_size(n), dtype=torch.uint8, device=dev)
+        sz = dev_get_values_plan(status, source, None, vloc, vlen, n, [], self.pool, ws, pool_bytes=self.pool_bytes)
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        out_vals = torch.empty(max(sz.val_bytes, 1), dtype=torch.uint8, device=dev)
+        dev_get_values_emit(status, source, None, vloc, vlen, n, [], self.pool, sz, ws, out_off, out_vals if sz.val_bytes else None,
+                            pool_bytes=self.pool_bytes)
+        torch.cuda.synchronize(dev)
+        return status.cpu().numpy(), out_off.cpu().numpy().view(np.uint64), out_vals.cpu().numpy()[: sz.val_bytes]
