@@ -1149,7 +1149,7 @@ int seb_wal_scan(const uint8_t *data, uint64_t bytes, uint64_t *rec_off, uint64_
  * from key to (segment, offset, size).  This group is its read side: what recover() (hashindex/recovery.go:14-141)
  * makes of the segment files, and what Get (hashindex/hashindex.go:217-260 -> segment.read, hashindex/segment.go:
  * 127-183) answers from them, for a key batch.  The write side (append's framing, segment rotation) and
- * compactSegments, whose output order is a Go map's, are out of scope.
+ * compactSegments are the next group.
  *
  * Layout: the caller holds the segment images back to back, OLDEST FIRST (ascending segment id), in one byte pool of
  * pool_bytes < 2^47, with per-segment host arrays seg_base[s] (the image's first byte in the pool) and seg_bytes[s].
@@ -1251,6 +1251,119 @@ int seb_dev_hidx_get(const void *table, uint64_t capacity, const uint8_t *pool, 
 int seb_hidx_recover(seb_ctx *ctx, const uint8_t *const *images, const uint64_t *image_bytes, uint64_t num_segments,
                      uint8_t *dev_pool, uint64_t pool_cap, void *dev_table, uint64_t capacity, uint64_t *valid,
                      uint64_t *size_after, uint8_t *short_tail, uint8_t *cut, uint64_t *records, uint64_t *live_records,
+                     uint64_t *distinct);
+
+/* ------------- hash index, write side: Put / Delete batches framed, segments compacted, the logical size ---- */
+/* FRAME.  HashIndex.Put / Delete -> segment.append (hashindex/segment.go:61-125): op i becomes the record above
+ * with `timestamp` (the reference's time.Now().Unix(); one per call: a caller that wants seconds to differ splits the
+ * batch); Delete is Put(key, nil): valueSize 0, whatever value bytes the op carries.  Inputs as seb_wal_frame_* takes
+ * them: keys in every seb_keys layout, vals + val_off (n + 1 non-decreasing offsets, val_off[0] may be != 0), deleted
+ * nullable.  ROTATION (hashindex.go:92-215): a record goes to the active segment iff that segment's size is below
+ * `limit` (SegmentSizeBytes, >= 1) BEFORE the append; otherwise the engine rotates once and the record opens the new
+ * segment.  With active_size = the active segment's size before the batch: cut[k] = the first op of the k-th new
+ * segment, ops [0, cut[0]) stay in the active one, and the image is the concatenation the engine splits at
+ * rec_off[cut[k]].
+ *
+ * Refusals, SEB_ERR_INVALID with seb_last_error naming the lowest offender ("op I"), checked for every op before a
+ * key or value byte is read and before anything is written: offsets that decrease; a key or a value of 2^32 bytes
+ * or more; an EMPTY KEY (Put refuses it, hashindex.go:92-95); keySize + valueSize >= 2^32 (the read side's stated
+ * departure; a Delete counts valueSize 0).  limit == 0: SEB_ERR_INVALID.  n < 2^32; n == 0 is valid and launches
+ * nothing.
+ *
+ * Host: seb_seg_frame_plan writes rec_off[0..n] (nullable), cut[0..*ncuts) (nullable: the cuts are only counted),
+ * *image_bytes and *ncuts (nullable).  cut_cap below the count: SEB_ERR_RANGE, *ncuts holds the need and nothing else
+ * is written.  seb_seg_frame_emit writes the sealed image into image[0, image_bytes) (image_bytes not the plan's:
+ * SEB_ERR_INVALID) and nothing outside it.
+ * Device: device pointers (offsets 8-byte aligned; keys, vals, deleted and the image at any byte alignment) except
+ * cut, image_bytes and ncuts, which are HOST memory.  seb_dev_seg_frame_plan writes rec_off[0..n] (required),
+ * SYNCHRONISES once and fills cut, *image_bytes and *ncuts (both required).  The cuts are a chain of bisections over
+ * rec_off in one lane, one link per new segment: a batch makes about image_bytes / limit of them.
+ * seb_dev_seg_frame_emit (not synchronised) writes the records and seals them (the segment CRC kernel's seal mode).
+ * Nothing is written outside the image and the n + 1 offsets, nothing is read outside the ops' arrays as their
+ * offsets describe them; rec_off is trusted as seb_dev_wal_frame_emit trusts it. */
+int seb_seg_frame_plan(const seb_keys *keys, const uint64_t *val_off, const uint8_t *deleted, uint64_t active_size,
+                       uint64_t limit, uint64_t *rec_off, uint64_t *cut, uint64_t cut_cap, uint64_t *image_bytes,
+                       uint64_t *ncuts);
+int seb_seg_frame_emit(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                       uint64_t timestamp, uint8_t *image, uint64_t image_bytes);
+int seb_dev_seg_frame_plan(const seb_keys *keys, const uint64_t *val_off, const uint8_t *deleted, uint64_t active_size,
+                           uint64_t limit, uint64_t *rec_off, uint64_t *cut, uint64_t cut_cap, uint64_t *image_bytes,
+                           uint64_t *ncuts, void *stream);
+int seb_dev_seg_frame_emit(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                           uint64_t timestamp, const uint64_t *rec_off, uint8_t *image, uint64_t image_bytes,
+                           void *stream);
+
+/* COMPACTION.  compactSegments (hashindex/compaction.go:12-76) walks the chosen segments in list order, each from
+ * offset 0; io.EOF (a short header, a payload past the end) ends that segment's walk silently, a CRC mismatch aborts
+ * the whole compaction.  Each clean record sets latestValues[key]: the last one wins AMONG THE CHOSEN SEGMENTS ONLY (a
+ * key with a newer record in an uncompacted segment is still written); keys whose winning value is empty are
+ * dropped; every other key is appended to a new segment with a fresh timestamp.  An empty key found in a segment is
+ * kept.  The reference writes the winners in a Go map's order; the SET is fully determined, and log order (the
+ * winners in ascending position) is one of the orders it can produce: that order is fixed here, so the compacted
+ * image is byte-exact.
+ *
+ * Input: the pool, and rec_off / live (nullable: all) for the records of the segments being compacted, in scan order
+ * (seb_seg_scan + seb_seg_verify; choosing the segments is the caller's job, and so is refusing a compaction whose
+ * verify found a bad record: these calls look at no CRC).  A live record that does not lie inside the pool:
+ * SEB_ERR_INVALID naming it ("record R").  Output: the survivors in record order, each with `timestamp` and a fresh
+ * CRC, and out_rec_off[0..survivors] = their offsets within the new image, ready for seb_dev_hidx_insert with the
+ * image as (part of) a pool.  Zero survivors: image_bytes == 0 and only out_rec_off[0] is written.
+ *
+ * Host: seb_seg_compact with image == NULL and out_rec_off == NULL only sizes; image_cap below image_bytes or rec_cap
+ * below survivors + 1 is SEB_ERR_RANGE with *sizes filled for a retry.
+ * Device: the workspace (seb_dev_seg_compact_workspace_size(num_records) bytes of device memory, 16-byte aligned,
+ * opaque; 0 for 2^38 records or more) carries the plan to the emit and must not be touched in between.  The plan builds
+ * a scratch key table in it from these records alone (seb_dev_hidx_insert's kernel; the test-only hidx_hash_mask
+ * applies), marks the survivors, scans their sizes, SYNCHRONISES and fills *sizes.  The emit (not synchronised; the
+ * same pool, rec_off and workspace) places the offsets, copies by OUTPUT BYTES (16 per lane, whatever record they
+ * belong to, so one long value does not hold a workgroup) and seals.  Its kernels check the workspace's header
+ * against `sizes` and write nothing where it is another plan's; every source record is re-checked against pool_bytes
+ * before a byte of it is read, and nothing is written outside image[0, image_bytes) and out_rec_off[0, survivors]. */
+typedef struct seb_segcompact_sizes {
+    uint64_t records_in, live_in;   /* the records given / those with live[r] != 0 */
+    uint64_t distinct, survivors;   /* keys among the live records / records written */
+    uint64_t tombstoned, shadowed;  /* keys dropped because their winning value is empty / live records that lost */
+    uint64_t image_bytes, reserved;
+} seb_segcompact_sizes;
+int seb_seg_compact(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                    uint64_t num_records, uint64_t timestamp, uint8_t *image, uint64_t image_cap, uint64_t *out_rec_off,
+                    uint64_t rec_cap, seb_segcompact_sizes *sizes);
+uint64_t seb_dev_seg_compact_workspace_size(uint64_t num_records);
+int seb_dev_seg_compact_plan(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                             uint64_t num_records, void *workspace, uint64_t workspace_bytes, seb_segcompact_sizes *sizes,
+                             void *stream);
+int seb_dev_seg_compact_emit(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t num_records,
+                             uint64_t timestamp, const seb_segcompact_sizes *sizes, void *workspace,
+                             uint64_t workspace_bytes, uint8_t *image, uint64_t *out_rec_off, void *stream);
+
+/* getLogicalSize (hashindex.go:360-385): the sum over the index entries, tombstoned keys included, of keySize +
+ * valueSize: the denominator of the "space amplification > 3.0" compaction trigger.  Host: over the live records'
+ * map, as seb_hidx_lookup builds it.  Device: a lane per slot of the table; SYNCHRONISES; *logical is HOST memory. */
+int seb_hidx_logical_size(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                          uint64_t num_records, uint64_t *logical);
+int seb_dev_hidx_logical_size(const void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes,
+                              uint64_t *logical, void *stream);
+
+/* compactSegments + applyCompaction on a context; synchronous.  dev_pool (DEVICE) holds the segments back to back,
+ * oldest first, as seg_base / seg_bytes (HOST, num_segments each) describe them; the oldest compact_segments >= 1 of
+ * them are compacted (choosing how many is the caller's job: doCompact's "oldest half").  Their bytes are scanned and
+ * verified; ANY BAD RECORD in them is SEB_ERR_INVALID naming "segment S: record R", as the reference aborts, and
+ * nothing is compacted; a short tail is not an error and its bytes are not copied.  Plan and emit go to the front of
+ * dst_pool (DEVICE, dst_cap bytes, not overlapping dev_pool); the segments that stay are copied behind the new
+ * image, and their live records' offsets rest_rec_off / rest_live (DEVICE; live nullable) are shifted:
+ * new_rec_off (DEVICE, new_rec_cap >= survivors + rest_records + 1 entries) = the survivors' offsets, the shifted
+ * ones, then the new pool's size.  dev_table is cleared and receives everything; the new image lies at the lowest
+ * offsets, so newer segments still win: the table equals the live index after applyCompaction (compaction.go:78-132),
+ * every Get answers as before, and *distinct drops by the keys whose latest record was a tombstone in a compacted
+ * segment.  Rebuilding rather than editing the table in place is deliberate: linear probing has no delete.  Host
+ * outputs: *sizes, new_seg_base / new_seg_bytes (num_segments - compact_segments + 1 each), *distinct (nullable).
+ * SEB_ERR_RANGE: dst_cap or new_rec_cap is below the need (*sizes and the new segment arrays are filled; nothing is
+ * written to the device outputs), or the table filled (seb_dev_hidx_count's rule). */
+int seb_hidx_compact(seb_ctx *ctx, const uint8_t *dev_pool, uint64_t pool_bytes, const uint64_t *seg_base,
+                     const uint64_t *seg_bytes, uint64_t num_segments, uint64_t compact_segments,
+                     const uint64_t *rest_rec_off, const uint8_t *rest_live, uint64_t rest_records, uint64_t timestamp,
+                     uint8_t *dst_pool, uint64_t dst_cap, void *dev_table, uint64_t capacity, uint64_t *new_rec_off,
+                     uint64_t new_rec_cap, seb_segcompact_sizes *sizes, uint64_t *new_seg_base, uint64_t *new_seg_bytes,
                      uint64_t *distinct);
 
 #ifdef __cplusplus

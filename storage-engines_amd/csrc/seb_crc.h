@@ -1,5 +1,6 @@
 // seb_crc.h — CRC-32 (IEEE) on the device, shared by the kernels that checksum records: k_wal_crc
-// (seb_codec.hip: WAL records) and k_seg_crc / k_hidx_get (seb_hashindex.hip: hash-index segment records).
+// (seb_codec.hip: WAL records) and k_seg_crc / k_hidx_get (seb_hashindex.hip: hash-index segment records; k_seg_crc's
+// seal mode writes the checksums of the records that seb_hashwrite.hip frames and compacts).
 // crc32.ChecksumIEEE: reflected polynomial 0xEDB88320, init ~0, final ~ (Go hash/crc32).
 // Slicing-by-4 tables, generated at compile time, staged in LDS per workgroup.
 #pragma once

@@ -6,7 +6,9 @@
 //   k_seg_crc      k_wal_crc's verify mode for the 20-byte header (the same staging and the same LDS walk, seb_crc.h),
 //                  with each record's length taken from its own header and checked against pool_bytes: a workgroup
 //                  owns 256 consecutive records, stages their span in LDS where it fits, and each lane checksums its
-//                  record.  A bad record's index goes into its segment's minimum (an agent-scope atomicMin).
+//                  record.  A bad record's index goes into its segment's minimum (an agent-scope atomicMin).  Its
+//                  seal mode (the write side) stores each record's checksum into its CRC field
+//                  instead of comparing it, as SEB_WAL_SEAL does for k_wal_crc; the field is not part of the checksum.
 //   k_seg_live     a lane per record: live[r] = r lies before its segment's first bad record
 //   k_seg_valid    a lane per segment: the minimum clamped to the segment's record count = valid[s]
 //   k_hidx_insert  a lane per live record into the open-addressing table (linear probing, a counted loop of at most
@@ -26,60 +28,21 @@
 #include <stdint.h>
 
 #include "seb_crc.h"
-#include "seb_device.h"
-#include "seb_hashindex.h"
-#include "seb_keycmp.h"
+#include "seb_hidx_dev.h"
 #include "seb_kernels.h"
 
 namespace seb {
 
 namespace {
 
-typedef unsigned long long u64a;  // what the 64-bit atomics take
-
-constexpr uint64_t kHeadBytes = 64;
-enum : uint32_t { hOverflow = 0, hCount = 1, hBad = 2 };  // the header's u64 words
-constexpr uint64_t kLow48 = (1ull << 48) - 1;
+constexpr uint64_t kHeadBytes = kHidxHeadBytes;
 constexpr uint32_t kSegRecs = 256;
 constexpr uint32_t kSegLds = 36 * 1024;  // k_wal_crc's window
 constexpr unsigned kStreamBlocks = 4096;  // most workgroups of a grid-stride launch
 
-#define HIDX_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
-}
-
-// The 8 bytes at p, little-endian, at any alignment: the two or three aligned dwords that cover them and a funnel
-// shift, instead of 8 byte loads.  Each of those dwords holds at least one of the 8 bytes, so none crosses into a
-// page the bytes do not touch (seb_device.h's fnv_range reads the same way).
-__device__ __forceinline__ uint64_t ld_u64_le(const uint8_t *p) {
-    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
-    const uint32_t *w = (const uint32_t *)((uintptr_t)p & ~(uintptr_t)3);
-    const uint32_t a0 = w[0], a1 = w[1];
-    if (sh == 0) return (uint64_t)a0 | (uint64_t)a1 << 32;
-    const uint32_t a2 = w[2];
-    return (uint64_t)__builtin_amdgcn_alignbyte(a1, a0, sh) | (uint64_t)__builtin_amdgcn_alignbyte(a2, a1, sh) << 32;
-}
-
-// seb_keycmp.h's two big-endian prefix words of a key of klen bytes
-__device__ __forceinline__ void prefix_words(const uint8_t *key, uint32_t klen, uint64_t &k0, uint64_t &k1) {
-    if (klen >= 16) {
-        k0 = __builtin_bswap64(ld_u64_le(key)), k1 = __builtin_bswap64(ld_u64_le(key + 8));
-    } else {
-        k0 = be64(key, klen), k1 = klen > 8 ? be64(key + 8, klen - 8) : 0ull;
-    }
-}
-
-// The record at pool offset `off` lies whole inside the pool and keySize + valueSize < 2^32 (seg_record of the
-// host half); no byte of the record is read before its header is known to fit.
-__device__ __forceinline__ bool rec_extent(const uint8_t *pool, uint64_t pool_bytes, uint64_t off, uint32_t *ks, uint32_t *vs) {
-    if (off > pool_bytes || pool_bytes - off < kSegHeader) return false;
-    const uint64_t sizes = ld_u64_le(pool + off + 12);
-    *ks = (uint32_t)sizes, *vs = (uint32_t)(sizes >> 32);
-    const uint64_t payload = (uint64_t)*ks + *vs;
-    return payload < (1ull << 32) && payload <= pool_bytes - off - kSegHeader;
 }
 
 // the last s < nseg with first[s] <= r (nseg >= 1)
@@ -92,8 +55,11 @@ __device__ __forceinline__ uint64_t seg_of(const uint64_t *__restrict__ first, u
     return lo;
 }
 
-template <uint32_t kLds>
-__global__ __launch_bounds__(kSegRecs) void k_seg_crc(const uint8_t *__restrict__ pool, uint64_t pool_bytes,
+// kSeal: the checksum of every record that lies inside the pool goes into its CRC field (bytes the walk above never
+// uses: a neighbouring workgroup's window may hold them, its checksums start 4 bytes further on); ok and first_bad
+// are not touched.
+template <uint32_t kLds, bool kSeal>
+__global__ __launch_bounds__(kSegRecs) void k_seg_crc(const uint8_t *pool, uint64_t pool_bytes,
                                                       const uint64_t *__restrict__ off, uint64_t n,
                                                       const uint64_t *__restrict__ seg_first, uint64_t nseg,
                                                       uint8_t *__restrict__ ok, u64a *__restrict__ first_bad) {
@@ -123,7 +89,8 @@ __global__ __launch_bounds__(kSegRecs) void k_seg_crc(const uint8_t *__restrict_
     const uint64_t i = r0 + threadIdx.x;
     if (i >= r1) return;
     const uint64_t s = off[i];
-    bool good = false;
+    bool good = false, whole = false;
+    uint32_t crc = 0;
     if (staged && s >= s0 && s <= el && el - s >= kSegHeader) {  // the header is in the window
         const uint8_t *lb = (const uint8_t *)stage;
         const uint32_t b = (uint32_t)((uintptr_t)(pool + s) - base);
@@ -131,12 +98,22 @@ __global__ __launch_bounds__(kSegRecs) void k_seg_crc(const uint8_t *__restrict_
         const uint64_t payload = (uint64_t)ks + vs;
         if (payload < (1ull << 32) && payload <= pool_bytes - s - kSegHeader) {
             const uint64_t e = s + kSegHeader + payload;
-            const uint32_t crc = e <= el ? crc_lds((const uint32_t *)stage, b + 4, (uint32_t)(kSegHeader - 4 + payload), tab)
-                                         : ~crc_range(~0u, pool, s + 4, e, tab);
-            good = crc == ld_u32_le(lb + b);
+            crc = e <= el ? crc_lds((const uint32_t *)stage, b + 4, (uint32_t)(kSegHeader - 4 + payload), tab)
+                          : ~crc_range(~0u, pool, s + 4, e, tab);
+            whole = true;
+            if constexpr (!kSeal) good = crc == ld_u32_le(lb + b);
         }
     } else if (rec_extent(pool, pool_bytes, s, &ks, &vs)) {
-        good = ~crc_range(~0u, pool, s + 4, s + kSegHeader + ks + vs, tab) == ld_u32_le(pool + s);
+        crc = ~crc_range(~0u, pool, s + 4, s + kSegHeader + ks + vs, tab);
+        whole = true;
+        if constexpr (!kSeal) good = crc == ld_u32_le(pool + s);
+    }
+    if constexpr (kSeal) {
+        if (whole) {
+            uint8_t *field = const_cast<uint8_t *>(pool) + s;
+            field[0] = (uint8_t)crc, field[1] = (uint8_t)(crc >> 8), field[2] = (uint8_t)(crc >> 16), field[3] = (uint8_t)(crc >> 24);
+        }
+        return;
     }
     ok[i] = good ? 1 : 0;
     if (!good && first_bad && nseg) {
@@ -160,34 +137,6 @@ __global__ __launch_bounds__(256) void k_seg_valid(const uint64_t *__restrict__ 
     if (sg >= nseg) return;
     const uint64_t a = seg_first[sg], b = seg_first[sg + 1], cnt = b > a ? b - a : 0;
     if (valid[sg] > cnt) valid[sg] = cnt;
-}
-
-// FNV-1a over the key bytes and a finishing mix (the tag is the hash's high 16 bits); hmask: the test-only option.
-__device__ __forceinline__ uint64_t hash_key(const uint8_t *p, uint32_t len, uint64_t hmask) {
-    uint64_t h = kFnvOffset;
-    uint32_t i = 0;
-    for (; i < len && (((uintptr_t)(p + i)) & 3u); ++i) h = (h ^ p[i]) * kFnvPrime;
-    for (; i + 4 <= len; i += 4) {
-        const uint32_t w = *(const uint32_t *)(p + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) h = (h ^ ((w >> (8 * j)) & 0xffu)) * kFnvPrime;
-    }
-    for (; i < len; ++i) h = (h ^ p[i]) * kFnvPrime;
-    h ^= h >> 29;
-    h *= 0xBF58476D1CE4E5B9ull;
-    h ^= h >> 32;
-    return hmask ? h & hmask : h;
-}
-
-// key (klen bytes, k0 / k1 its first 16 as seb_keycmp.h holds them) equals the key of the record at `o`, which is
-// checked against the pool first; *oks / *ovs are then that record's sizes
-__device__ __forceinline__ bool same_key(const uint8_t *pool, uint64_t pool_bytes, uint64_t o, const uint8_t *key,
-                                         uint32_t klen, uint64_t k0, uint64_t k1, uint32_t *oks, uint32_t *ovs) {
-    if (!rec_extent(pool, pool_bytes, o, oks, ovs) || *oks != klen) return false;
-    const uint8_t *stored = pool + o + kSegHeader;
-    uint64_t be[2];
-    prefix_words(stored, klen, be[0], be[1]);
-    return cmp_key(key, klen, k0, k1, be, stored, klen) == 0;
 }
 
 // 1: the record claimed an empty slot (a new key)
@@ -330,11 +279,20 @@ hipError_t launch_seg_verify(const uint8_t *pool, uint64_t pool_bytes, const uin
     if (n) {
         const uint64_t g = (n + kSegRecs - 1) / kSegRecs;
         if (g >= (1ull << 31)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_seg_crc<kSegLds>, dim3((unsigned)g), dim3(kSegRecs), 0, s, pool, pool_bytes, rec_off, n, seg_first,
-                           nseg, ok, (u64a *)valid);
+        hipLaunchKernelGGL((k_seg_crc<kSegLds, false>), dim3((unsigned)g), dim3(kSegRecs), 0, s, pool, pool_bytes, rec_off, n,
+                           seg_first, nseg, ok, (u64a *)valid);
         if (live && nseg) hipLaunchKernelGGL(k_seg_live, dim3(stream_grid(n)), dim3(256), 0, s, seg_first, nseg, n, valid, live);
     }
     if (nseg) hipLaunchKernelGGL(k_seg_valid, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, s, seg_first, nseg, valid);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_seal(uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t g = (n + kSegRecs - 1) / kSegRecs;
+    if (g >= (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_seg_crc<kSegLds, true>), dim3((unsigned)g), dim3(kSegRecs), 0, s, (const uint8_t *)pool, pool_bytes,
+                       rec_off, n, (const uint64_t *)nullptr, (uint64_t)0, (uint8_t *)nullptr, (u64a *)nullptr);
     return hipGetLastError();
 }
 

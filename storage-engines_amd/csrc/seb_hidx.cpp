@@ -1,8 +1,10 @@
-// seb_hidx.cpp — the hash index's entry points: the C ABI over its host half (seb_hashindex.cpp)
-// and its kernels (seb_hashindex.hip), and seb_hidx_recover, recover() on host images through a context.
+// seb_hidx.cpp — the hash index's entry points: the C ABI over its host halves
+// (seb_hashindex.cpp, seb_hashwrite.cpp) and its kernels (seb_hashindex.hip, seb_hashwrite.hip), and seb_hidx_recover,
+// recover() on host images through a context.
 #include <new>
 
 #include "seb_hashindex.h"
+#include "seb_hashwrite.h"
 #include "seb_host.h"
 
 using namespace seb;
@@ -237,6 +239,341 @@ extern "C" int seb_hidx_recover(seb_ctx *c, const uint8_t *const *images, const 
     if (count_rc == SEB_ERR_RANGE)
         return fail(SEB_ERR_RANGE, "%s: the table filled: more than %llu distinct keys; retry with a capacity of the %llu live "
                     "records at most", who, (unsigned long long)capacity, (unsigned long long)alive);
+    if (distinct) *distinct = keys;
+    return SEB_OK;
+}
+
+// ------------------------------------------------ write side
+
+static_assert(sizeof(seb_segcompact_sizes) == sizeof(seb::SegCompactSizes) && sizeof(seb_segcompact_sizes) == 64,
+              "seb_segcompact_sizes layout");
+
+static int segframe_rc(int rc, uint64_t op, uint64_t need, const char *who) {
+    const unsigned long long i = (unsigned long long)op;
+    switch (rc) {
+    case 0:
+        return SEB_OK;
+    case -2:
+        return fail(SEB_ERR_INVALID, "%s: op %llu: its key offsets decrease or its key has 2^32 bytes or more", who, i);
+    case -3:
+        return fail(SEB_ERR_INVALID, "%s: op %llu: its value offsets decrease or its value has 2^32 bytes or more", who, i);
+    case -4:
+        return fail(SEB_ERR_INVALID, "%s: 2^32 ops or more", who);
+    case -5:
+        return fail(SEB_ERR_INVALID, "%s: image_bytes is not this batch's plan", who);
+    case -6:
+        return fail(SEB_ERR_INVALID, "%s: op %llu: an empty key (Put refuses it)", who, i);
+    case -7:
+        return fail(SEB_ERR_INVALID, "%s: op %llu: keySize + valueSize is 2^32 or more", who, i);
+    case -8:
+        return fail(SEB_ERR_RANGE, "%s: cut_cap is below the batch's %llu cuts", who, (unsigned long long)need);
+    case -9:
+        return fail(SEB_ERR_INVALID, "%s: limit is 0", who);
+    default:
+        return fail(SEB_ERR_INVALID, "%s: null argument", who);
+    }
+}
+
+static int check_seg_ops(const seb_keys *keys, const uint64_t *val_off, const char *who) {
+    int rc;
+    if ((rc = check_keys(keys, who))) return rc;
+    if (keys->n >= (1ull << 32)) return segframe_rc(-4, 0, 0, who);
+    if (keys->n && !val_off) return segframe_rc(-1, 0, 0, who);
+    return SEB_OK;
+}
+
+extern "C" int seb_seg_frame_plan(const seb_keys *keys, const uint64_t *val_off, const uint8_t *deleted, uint64_t active_size,
+                                  uint64_t limit, uint64_t *rec_off, uint64_t *cut, uint64_t cut_cap, uint64_t *image_bytes,
+                                  uint64_t *ncuts) {
+    const char *who = "seb_seg_frame_plan";
+    int rc;
+    if ((rc = check_seg_ops(keys, val_off, who))) return rc;
+    uint64_t op = 0, cuts = 0;
+    rc = seb::seg_frame_plan(KeysView{keys->data, keys->offsets, keys->n, keys->stride}, val_off, deleted, active_size, limit,
+                             rec_off, cut, cut_cap, image_bytes, &cuts, &op);
+    if (ncuts && (rc == 0 || rc == -8)) *ncuts = cuts;
+    return segframe_rc(rc, op, cuts, who);
+}
+
+extern "C" int seb_seg_frame_emit(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                                  uint64_t timestamp, uint8_t *image, uint64_t image_bytes) {
+    const char *who = "seb_seg_frame_emit";
+    int rc;
+    if ((rc = check_seg_ops(keys, val_off, who))) return rc;
+    uint64_t op = 0;
+    rc = seb::seg_frame_emit(KeysView{keys->data, keys->offsets, keys->n, keys->stride}, vals, val_off, deleted, timestamp,
+                             image, image_bytes, &op);
+    return segframe_rc(rc, op, 0, who);
+}
+
+static int check_dev_seg_ops(const seb_keys *keys, const uint64_t *val_off, const char *who) {
+    int rc;
+    if ((rc = check_seg_ops(keys, val_off, who))) return rc;
+    if (keys->n && (((uintptr_t)keys->offsets & 7) || ((uintptr_t)val_off & 7)))
+        return fail(SEB_ERR_INVALID, "%s: offsets that are not 8-byte aligned", who);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_seg_frame_plan(const seb_keys *keys, const uint64_t *val_off, const uint8_t *deleted,
+                                      uint64_t active_size, uint64_t limit, uint64_t *rec_off, uint64_t *cut, uint64_t cut_cap,
+                                      uint64_t *image_bytes, uint64_t *ncuts, void *stream) {
+    const char *who = "seb_dev_seg_frame_plan";
+    WsCall ws_call;
+    enter();
+    int rc;
+    if ((rc = check_dev_seg_ops(keys, val_off, who))) return rc;
+    if (!image_bytes || !ncuts) return segframe_rc(-1, 0, 0, who);
+    if (limit == 0) return segframe_rc(-9, 0, 0, who);
+    *image_bytes = *ncuts = 0;
+    if (keys->n == 0) return SEB_OK;
+    if (!rec_off || ((uintptr_t)rec_off & 7)) return fail(SEB_ERR_INVALID, "%s: rec_off is null or not 8-byte aligned", who);
+    if (!cut) cut_cap = 0;
+    hipStream_t s = (hipStream_t)stream;
+    void *scratch = nullptr;
+    if ((rc = cached_workspace(s, segframe_scratch_bytes(keys->n, cut_cap), &scratch, 5))) return rc;
+    const uint64_t slots = cut_cap < keys->n ? cut_cap : keys->n;
+    std::vector<uint64_t> got;
+    try {
+        got.resize(slots);
+    } catch (const std::bad_alloc &) {
+        return hidx_rc(-3, who);
+    }
+    uint64_t h[3] = {0, 0, 0};
+    HIP_OR_FAIL(launch_segframe_plan(key_batch(keys), val_off, deleted, active_size, limit, rec_off, got.data(), cut_cap, scratch, h,
+                                     s));
+    if (h[0] != UINT64_MAX) {
+        static const int why[4] = {-2, -3, -6, -7};
+        return segframe_rc(why[h[0] & 3], h[0] >> 2, 0, who);
+    }
+    *image_bytes = h[1];
+    *ncuts = h[2];
+    if (cut && h[2] > cut_cap) return segframe_rc(-8, 0, h[2], who);
+    if (cut && h[2]) memcpy(cut, got.data(), 8 * h[2]);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_seg_frame_emit(const seb_keys *keys, const uint8_t *vals, const uint64_t *val_off,
+                                      const uint8_t *deleted, uint64_t timestamp, const uint64_t *rec_off, uint8_t *image,
+                                      uint64_t image_bytes, void *stream) {
+    const char *who = "seb_dev_seg_frame_emit";
+    enter();
+    int rc;
+    if ((rc = check_dev_seg_ops(keys, val_off, who))) return rc;
+    const uint64_t n = keys->n;
+    if (n == 0) return image_bytes ? segframe_rc(-5, 0, 0, who) : SEB_OK;
+    if (!rec_off || ((uintptr_t)rec_off & 7) || !image)
+        return fail(SEB_ERR_INVALID, "%s: null image, or rec_off null or not 8-byte aligned", who);
+    // a record has 21 bytes at least (the header and a key byte) and 20 + 2^32 - 1 at most
+    if (image_bytes < 21 * n || image_bytes > n * (20 + 0xFFFFFFFFull) || image_bytes >= seb::kHidxPoolLimit)
+        return segframe_rc(-5, 0, 0, who);
+    HIP_OR_FAIL(launch_segframe_emit(key_batch(keys), vals, val_off, deleted, timestamp, rec_off, image, image_bytes,
+                                     (hipStream_t)stream));
+    return SEB_OK;
+}
+
+static int compact_rc(int rc, uint64_t bad, const seb_segcompact_sizes *sz, const char *who) {
+    switch (rc) {
+    case -4:
+        return fail(SEB_ERR_INVALID, "%s: record %llu does not lie inside the pool, or its keySize + valueSize is 2^32 or more",
+                    who, (unsigned long long)bad);
+    case -5:
+        return fail(SEB_ERR_RANGE, "%s: a capacity is below the compaction's sizes: %llu image bytes, %llu + 1 offsets", who,
+                    (unsigned long long)sz->image_bytes, (unsigned long long)sz->survivors);
+    default:
+        return hidx_rc(rc, who);
+    }
+}
+
+extern "C" int seb_seg_compact(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                               uint64_t num_records, uint64_t timestamp, uint8_t *image, uint64_t image_cap,
+                               uint64_t *out_rec_off, uint64_t rec_cap, seb_segcompact_sizes *sizes) {
+    const char *who = "seb_seg_compact";
+    uint64_t bad = 0;
+    const int rc = seb::seg_compact(pool, pool_bytes, rec_off, live, num_records, timestamp, image, image_cap, out_rec_off, rec_cap,
+                                    (seb::SegCompactSizes *)sizes, &bad);
+    return compact_rc(rc, bad, sizes, who);
+}
+
+extern "C" int seb_hidx_logical_size(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                                     uint64_t num_records, uint64_t *logical) {
+    return hidx_rc(seb::hidx_logical_size(pool, pool_bytes, rec_off, live, num_records, logical), "seb_hidx_logical_size");
+}
+
+extern "C" uint64_t seb_dev_seg_compact_workspace_size(uint64_t num_records) {
+    return num_records >= (1ull << 38) ? 0 : segcompact_ws_layout(num_records ? num_records : 1).bytes;
+}
+
+static int check_compact(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t n, const void *ws,
+                         uint64_t ws_bytes, const char *who) {
+    int rc;
+    if ((rc = check_pool(pool, pool_bytes, who))) return rc;
+    if (n >= (1ull << 38)) return fail(SEB_ERR_INVALID, "%s: 2^38 records or more", who);
+    if (n && (!rec_off || ((uintptr_t)rec_off & 7))) return fail(SEB_ERR_INVALID, "%s: rec_off is null or not 8-byte aligned", who);
+    if (n && (!ws || ((uintptr_t)ws & 15) || ws_bytes < segcompact_ws_layout(n).bytes))
+        return fail(SEB_ERR_INVALID, "%s: the workspace is null, not 16-byte aligned or below %llu bytes", who,
+                    (unsigned long long)segcompact_ws_layout(n).bytes);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_seg_compact_plan(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                                        uint64_t num_records, void *workspace, uint64_t workspace_bytes,
+                                        seb_segcompact_sizes *sizes, void *stream) {
+    const char *who = "seb_dev_seg_compact_plan";
+    enter();
+    int rc;
+    if (!sizes) return hidx_rc(-1, who);
+    *sizes = seb_segcompact_sizes{num_records, 0, 0, 0, 0, 0, 0, 0};
+    if ((rc = check_compact(pool, pool_bytes, rec_off, num_records, workspace, workspace_bytes, who))) return rc;
+    if (num_records == 0) return SEB_OK;
+    uint64_t h[8];
+    HIP_OR_FAIL(launch_segcompact_plan(pool, pool_bytes, rec_off, live, num_records, options().hidx_hash_mask, workspace, h,
+                                       (hipStream_t)stream));
+    if (h[0] != UINT64_MAX) return compact_rc(-4, h[0], sizes, who);
+    if (h[6]) return fail(SEB_ERR_INTERNAL, "%s: the scratch table filled", who);
+    *sizes = seb_segcompact_sizes{num_records, h[1], h[2], h[3], h[4], h[1] - h[2], h[5], 0};
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_seg_compact_emit(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t num_records,
+                                        uint64_t timestamp, const seb_segcompact_sizes *sizes, void *workspace,
+                                        uint64_t workspace_bytes, uint8_t *image, uint64_t *out_rec_off, void *stream) {
+    const char *who = "seb_dev_seg_compact_emit";
+    enter();
+    int rc;
+    if (!sizes) return hidx_rc(-1, who);
+    if ((rc = check_compact(pool, pool_bytes, rec_off, num_records, workspace, workspace_bytes, who))) return rc;
+    if (sizes->records_in != num_records || sizes->survivors > num_records || sizes->image_bytes < 21 * sizes->survivors ||
+        (sizes->survivors == 0 && sizes->image_bytes) || sizes->image_bytes >= seb::kHidxPoolLimit)
+        return fail(SEB_ERR_INVALID, "%s: sizes are not these records' plan", who);
+    if (!out_rec_off || ((uintptr_t)out_rec_off & 7) || (sizes->image_bytes && !image))
+        return fail(SEB_ERR_INVALID, "%s: null image, or out_rec_off null or not 8-byte aligned", who);
+    HIP_OR_FAIL(launch_segcompact_emit(pool, pool_bytes, rec_off, num_records, timestamp, sizes->survivors, sizes->image_bytes,
+                                       workspace, image, out_rec_off, (hipStream_t)stream));
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_hidx_logical_size(const void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes,
+                                         uint64_t *logical, void *stream) {
+    const char *who = "seb_dev_hidx_logical_size";
+    WsCall ws_call;
+    enter();
+    int rc;
+    if ((rc = check_table(table, capacity, who)) || (rc = check_pool(pool, pool_bytes, who))) return rc;
+    if (!logical) return hidx_rc(-1, who);
+    *logical = 0;
+    hipStream_t s = (hipStream_t)stream;
+    void *scratch = nullptr;
+    if ((rc = cached_workspace(s, 16, &scratch, 5))) return rc;
+    HIP_OR_FAIL(launch_hidx_logical(table, capacity, pool, pool_bytes, (uint64_t *)scratch, logical, s));
+    return SEB_OK;
+}
+
+// compactSegments + applyCompaction on a pool in device memory: the compacted segments' bytes come down for the
+// framing walk alone (the walk is sequential); verify, plan, emit, the copy of the segments that stay, the shift of
+// their offsets, clear and insert run on the compute stream.
+extern "C" int seb_hidx_compact(seb_ctx *c, const uint8_t *dev_pool, uint64_t pool_bytes, const uint64_t *seg_base,
+                                const uint64_t *seg_bytes, uint64_t num_segments, uint64_t compact_segments,
+                                const uint64_t *rest_rec_off, const uint8_t *rest_live, uint64_t rest_records, uint64_t timestamp,
+                                uint8_t *dst_pool, uint64_t dst_cap, void *dev_table, uint64_t capacity, uint64_t *new_rec_off,
+                                uint64_t new_rec_cap, seb_segcompact_sizes *sizes, uint64_t *new_seg_base,
+                                uint64_t *new_seg_bytes, uint64_t *distinct) {
+    const char *who = "seb_hidx_compact";
+    int rc;
+    if (!c) return fail(SEB_ERR_INVALID, "%s: null ctx", who);
+    if (!sizes || !seg_base || !seg_bytes || !new_seg_base || !new_seg_bytes) return hidx_rc(-1, who);
+    *sizes = seb_segcompact_sizes{0, 0, 0, 0, 0, 0, 0, 0};
+    if (distinct) *distinct = 0;
+    const uint64_t cs = compact_segments;
+    if (cs == 0 || cs > num_segments || num_segments >= (1ull << 32))
+        return fail(SEB_ERR_INVALID, "%s: %llu of %llu segments", who, (unsigned long long)cs, (unsigned long long)num_segments);
+    if ((rc = check_table(dev_table, capacity, who)) || (rc = check_pool(dev_pool, pool_bytes, who))) return rc;
+    uint64_t at = seg_base[0];
+    for (uint64_t s = 0; s < num_segments; ++s) {  // back to back, oldest first, inside the pool
+        if (seg_base[s] != at || seg_bytes[s] > pool_bytes - at)
+            return fail(SEB_ERR_INVALID, "%s: segment %llu does not lie behind its predecessor inside the pool", who,
+                        (unsigned long long)s);
+        at += seg_bytes[s];
+    }
+    const uint64_t head_at = seg_base[0], rest_at = seg_base[cs - 1] + seg_bytes[cs - 1], head_bytes = rest_at - head_at,
+                   rest_bytes = at - rest_at;
+    if (rest_records >= (1ull << 38)) return fail(SEB_ERR_INVALID, "%s: 2^38 records or more", who);
+    if (rest_records && (!rest_rec_off || ((uintptr_t)rest_rec_off & 7)))
+        return fail(SEB_ERR_INVALID, "%s: rest_rec_off is null or not 8-byte aligned", who);
+    if (!new_rec_off || ((uintptr_t)new_rec_off & 7)) return fail(SEB_ERR_INVALID, "%s: new_rec_off is null or not 8-byte aligned", who);
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OR_FAIL(hipSetDevice(c->device));
+    hipStream_t st = c->s_comp;
+    struct Drain {
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{st};
+    std::vector<uint8_t> head;
+    std::vector<uint64_t> off, first, dvalid;
+    try {
+        head.resize(head_bytes);
+        if (head_bytes) {
+            HIP_OR_FAIL(hipMemcpyAsync(head.data(), dev_pool + head_at, head_bytes, hipMemcpyDeviceToHost, st));
+            HIP_OR_FAIL(hipStreamSynchronize(st));
+        }
+        first.resize(cs + 1);
+        dvalid.resize(cs);
+        uint64_t n = 0;
+        for (uint64_t s = 0; s < cs; ++s) {
+            first[s] = n;
+            off.resize(n + seg_bytes[s] / seb::kSegHeader + 1);
+            uint64_t got = 0;
+            int tail = 0;
+            if (seb::seg_scan(head.data() + (seg_base[s] - head_at), seg_bytes[s], seg_base[s], off.data() + n, off.size() - n, &got,
+                              &tail) != 0)
+                return fail(SEB_ERR_INTERNAL, "%s: segment %llu: the scan ran past its bound", who, (unsigned long long)s);
+            n += got;  // a short tail is no record: its bytes are not copied
+        }
+        first[cs] = n;
+        off.resize(n);
+        std::vector<uint8_t>().swap(head);
+    } catch (const std::bad_alloc &) {
+        return hidx_rc(-3, who);
+    }
+    const uint64_t n = off.size();
+    if (n >= (1ull << 38)) return fail(SEB_ERR_INVALID, "%s: 2^38 records or more", who);
+    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t a_first = up(8 * n), a_valid = a_first + up(8 * (cs + 1)), a_ok = a_valid + up(8 * cs), a_live = a_ok + up(n),
+                   a_plan = a_live + up(n), plan_bytes = n ? segcompact_ws_layout(n).bytes : 0;
+    if ((rc = c->hx_ws.reserve(a_plan + plan_bytes + 16))) return rc;
+    uint8_t *w = (uint8_t *)c->hx_ws.p;
+    if (n) HIP_OR_FAIL(hipMemcpyAsync(w, off.data(), 8 * n, hipMemcpyHostToDevice, st));
+    HIP_OR_FAIL(hipMemcpyAsync(w + a_first, first.data(), 8 * (cs + 1), hipMemcpyHostToDevice, st));
+    if ((rc = seb_dev_seg_verify(dev_pool, pool_bytes, (const uint64_t *)w, n, (const uint64_t *)(w + a_first), cs, w + a_ok,
+                                 (uint64_t *)(w + a_valid), w + a_live, st)))
+        return rc;
+    HIP_OR_FAIL(hipMemcpyAsync(dvalid.data(), w + a_valid, 8 * cs, hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    for (uint64_t s = 0; s < cs; ++s)  // compactSegments returns the error: nothing is compacted
+        if (dvalid[s] < first[s + 1] - first[s])
+            return fail(SEB_ERR_INVALID, "%s: segment %llu: record %llu fails its CRC: the compaction is aborted", who,
+                        (unsigned long long)s, (unsigned long long)dvalid[s]);
+    if ((rc = seb_dev_seg_compact_plan(dev_pool, pool_bytes, (const uint64_t *)w, nullptr, n, w + a_plan, plan_bytes, sizes, st)))
+        return rc;
+    const uint64_t image = sizes->image_bytes, surv = sizes->survivors, total = image + rest_bytes;
+    new_seg_base[0] = 0, new_seg_bytes[0] = image;
+    for (uint64_t s = cs; s < num_segments; ++s)
+        new_seg_base[s - cs + 1] = seg_base[s] - rest_at + image, new_seg_bytes[s - cs + 1] = seg_bytes[s];
+    if (total > dst_cap || surv + rest_records + 1 > new_rec_cap)
+        return fail(SEB_ERR_RANGE, "%s: the new pool needs %llu bytes and %llu offsets", who, (unsigned long long)total,
+                    (unsigned long long)(surv + rest_records + 1));
+    if (total >= seb::kHidxPoolLimit) return hidx_rc(-2, who);
+    if (total && !dst_pool) return fail(SEB_ERR_INVALID, "%s: null destination pool", who);
+    if ((rc = seb_dev_seg_compact_emit(dev_pool, pool_bytes, (const uint64_t *)w, n, timestamp, sizes, w + a_plan, plan_bytes, dst_pool,
+                                       new_rec_off, st)))
+        return rc;
+    if (rest_bytes) HIP_OR_FAIL(hipMemcpyAsync(dst_pool + image, dev_pool + rest_at, rest_bytes, hipMemcpyDeviceToDevice, st));
+    HIP_OR_FAIL(launch_offsets_shift(rest_rec_off, rest_records, rest_at, image, new_rec_off + surv, total, st));
+    if ((rc = seb_dev_hidx_clear(dev_table, capacity, st))) return rc;
+    // the new image lies at the lowest offsets, so the segments that stay still win
+    if ((rc = seb_dev_hidx_insert(dev_table, capacity, dst_pool, total, new_rec_off, nullptr, surv, st))) return rc;
+    if ((rc = seb_dev_hidx_insert(dev_table, capacity, dst_pool, total, new_rec_off + surv, rest_live, rest_records, st))) return rc;
+    uint64_t keys = 0;
+    if ((rc = seb_dev_hidx_count(dev_table, capacity, &keys, nullptr, st))) return rc;  // synchronises
     if (distinct) *distinct = keys;
     return SEB_OK;
 }

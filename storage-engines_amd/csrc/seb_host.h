@@ -23,7 +23,10 @@
 //   seb_hashindex.cpp the host half of the hash index's read side: segment scan, verify and cuts, Get (no HIP
 //                     dependency; seb_hashindex.h)
 //   seb_hashindex.hip its kernels: segment CRC, live flags, table insert, Get (the CRC itself: seb_crc.h)
-//   seb_hidx.cpp      the hash index's entry points and seb_hidx_recover
+//   seb_hashwrite.cpp the host half of the hash index's write side: frame and cuts, compaction, logical size (no HIP
+//                     dependency; seb_hashwrite.h)
+//   seb_hashwrite.hip its kernels (the seal: k_seg_crc's seal mode in seb_hashindex.hip; what both share: seb_hidx_dev.h)
+//   seb_hidx.cpp      the hash index's entry points, seb_hidx_recover and seb_hidx_compact
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -238,7 +241,8 @@ struct seb_ctx {
     seb::DevBuf mg_runs, mg_out;  // seb_memtable_get: the runs' arrays and indexes, a chunk's six output arrays
     seb::DevBuf mw_in, mw_img, mw_ws, mw_out, mw_runs;  // seb_memtable_apply / _fold: the ops + rec_off + delta, the image,
                                                          // the plan's workspace, the run's six arrays, the runs + indexes
-    seb::DevBuf hx_ws;  // seb_hidx_recover: rec_off + seg_first + valid + ok + live
+    seb::DevBuf hx_ws;  // seb_hidx_recover: rec_off + seg_first + valid + ok + live; seb_hidx_compact: the same and the plan's
+                        // workspace
     seb::PinBuf hkeys, hbits;  // small filter builds: keys in, bits out, read and written by the kernels
     uint64_t chunk_bytes = 64ull << 20;
     std::vector<uint64_t> off_tmp[2];

@@ -405,6 +405,45 @@ hipError_t launch_hidx_get(const void *table, uint64_t capacity, const uint8_t *
                            bool verify, uint64_t hash_mask, uint8_t *status, uint64_t *rec, uint64_t *vloc, uint32_t *vlen,
                            uint8_t *source, hipStream_t s);
 
+// k_seg_crc's seal mode: the checksum of every record rec_off names that lies inside pool[0, pool_bytes) goes into
+// its CRC field.
+hipError_t launch_seg_seal(uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t n, hipStream_t s);
+
+// seb_hashwrite.hip: the hash index's write side (the semantics: seb_hashwrite.h).
+uint64_t segframe_scratch_bytes(uint64_t n, uint64_t cut_cap);  // device scratch of launch_segframe_plan
+// n >= 1, limit >= 1.  rec_off: n + 1 device u64.  Synchronises the stream; out_host = [the least bad op << 2 | (0 key
+// offsets, 1 value offsets, 2 empty key, 3 keySize + valueSize), all ones for none][the image's size][the cuts'
+// count]; cut_host (HOST memory of min(cut_cap, n) entries, nullable) receives the first min(cut_cap, n, count) cuts
+// (entries behind them may be written too).
+hipError_t launch_segframe_plan(const KeyBatch &kb, const uint64_t *val_off, const uint8_t *deleted, uint64_t active_size,
+                                uint64_t limit, uint64_t *rec_off, uint64_t *cut_host, uint64_t cut_cap, void *scratch,
+                                uint64_t out_host[3], hipStream_t s);
+// n >= 1, image_bytes >= 1.  Writes the sealed image[0, image_bytes); nothing else is written.
+hipError_t launch_segframe_emit(const KeyBatch &kb, const uint8_t *vals, const uint64_t *val_off, const uint8_t *deleted,
+                                uint64_t timestamp, const uint64_t *rec_off, uint8_t *image, uint64_t image_bytes,
+                                hipStream_t s);
+// The compaction's plan lives in a caller-provided workspace: a 64-byte header, a scratch key table of capacity n,
+// the tiles' two sums, then per record its output offset, a survivor's source offset and its mark.
+struct SegCompactWs {
+    uint64_t bytes, tiles, table, sums, pos, src, mark;
+};
+SegCompactWs segcompact_ws_layout(uint64_t n);
+// n >= 1, < 2^38.  Synchronises; out_host = [the least live record outside the pool, all ones for none][live records]
+// [distinct keys][survivors][tombstoned keys][image bytes][the scratch table overflowed][winning records].
+hipError_t launch_segcompact_plan(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, const uint8_t *live,
+                                  uint64_t n, uint64_t hash_mask, void *ws, uint64_t out_host[8], hipStream_t s);
+// Nothing is written unless ws holds the plan that returned (survivors, image_bytes), and nothing outside
+// image[0, image_bytes) and out_rec_off[0, survivors] in any case.  survivors == 0: only out_rec_off[0].
+hipError_t launch_segcompact_emit(const uint8_t *pool, uint64_t pool_bytes, const uint64_t *rec_off, uint64_t n,
+                                  uint64_t timestamp, uint64_t survivors, uint64_t image_bytes, void *ws, uint8_t *image,
+                                  uint64_t *out_rec_off, hipStream_t s);
+// dst[0, n) = src[i] - sub + add (all ones where src[i] < sub), dst[n] = end
+hipError_t launch_offsets_shift(const uint64_t *src, uint64_t n, uint64_t sub, uint64_t add, uint64_t *dst, uint64_t end,
+                                hipStream_t s);
+// Synchronises; *sum_host = keySize + valueSize over the records the table names; sum_dev: 8 bytes of device scratch.
+hipError_t launch_hidx_logical(const void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes,
+                               uint64_t *sum_dev, uint64_t *sum_host, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

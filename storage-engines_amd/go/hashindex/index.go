@@ -1,4 +1,4 @@
-// The read side of the hash index, over the hash index group of libseb_bloom (include/seb_bloom.h): what
+// The hash index, over the hash index groups of libseb_bloom (include/seb_bloom.h): what
 // recover() (hashindex/recovery.go) makes of the segment files, and what Get (hashindex/hashindex.go:217-260 ->
 // segment.read) answers from them, for a key batch.
 //
@@ -12,12 +12,25 @@
 //	DevInsert records appended to the active segment into the same table (seb_dev_seg_verify, seb_dev_hidx_insert,
 //	          seb_dev_hidx_count)
 //
+//	Frame     a Put / Delete batch as segment.append's sealed records in device memory, with the rotation's cuts
+//	          (seb_dev_seg_frame_plan, seb_dev_seg_frame_emit); FrameHost is the same on the host
+//	Compact   compactSegments + applyCompaction for the oldest c segments of a device pool (seb_hidx_compact): the
+//	          survivors in log order at the front of a new pool, the other segments behind, the table rebuilt
+//	LogicalSize getLogicalSize over the table (seb_dev_hidx_logical_size)
+//
 // One stated departure: a header with keySize + valueSize >= 2^32 counts as a CRC failure and cuts its segment; the
-// reference adds the two as uint32 and then fails the CRC or panics on the slice.  The write side (append's framing,
-// segment rotation) and compactSegments are not here.
+// reference adds the two as uint32 and then fails the CRC or panics on the slice.
+//
+// NAMING THE COMPACTED FILE.  The reference names the compacted segment with the current time, so its id is above
+// every segment it did not compact, and after a restart its own recover() replays the compacted (older) records over
+// newer ones.  The table Compact leaves equals the live index after applyCompaction: the compacted image lies at the
+// LOWEST pool offsets, so newer segments still win.  An engine that wants recover() to rebuild that same index must
+// name the compacted file so that it sorts BEFORE the segments it did not compact (the id of the newest compacted
+// segment, say).
 //
 // Not compiled in this repository's pipeline (no Go toolchain in the image); the C ABI it calls is tested through
-// the Python binding (tests/test_hashindex.py, tests/test_gpu_hashindex.py).
+// the Python binding (tests/test_hashindex.py, tests/test_gpu_hashindex.py, tests/test_hashwrite.py,
+// tests/test_gpu_hashwrite.py).
 package hashindex
 
 /*
@@ -223,4 +236,124 @@ func DevClear(table unsafe.Pointer, capacity uint64, stream unsafe.Pointer) erro
 		return lastError("failed to clear the hash index")
 	}
 	return nil
+}
+
+// Ops is a Put / Delete batch in device memory: keys in DevKeys' layouts, op i's value = Vals[ValOff[i]:ValOff[i+1]]
+// (ValOff: n + 1 u64, ValOff[0] may be != 0), Deleted (nil: none) one byte per op; a Delete's value bytes are ignored.
+type Ops struct {
+	Keys                  DevKeys
+	Vals, ValOff, Deleted unsafe.Pointer
+}
+
+// Framed is what a frame plan returns: the image's size and, for rotation at `limit` behind activeSize bytes of the
+// active segment, the first op of each new segment.  Ops [0, Cuts[0]) stay in the active one; the engine splits the
+// image at recOff[Cuts[k]].
+type Framed struct {
+	ImageBytes uint64
+	Cuts       []uint64
+}
+
+// ErrCuts is returned with Framed.Cuts sized to the need where cutCap was too small.
+var ErrCuts = fmt.Errorf("more cuts than cutCap")
+
+// FramePlan sizes the batch: recOff (n + 1 device u64) is written, the call synchronises.  An empty key, a key or a
+// value of 2^32 bytes or more, keySize + valueSize >= 2^32 and offsets that decrease are refused, naming the op.
+func FramePlan(ops Ops, activeSize, limit uint64, recOff unsafe.Pointer, cutCap uint64, stream unsafe.Pointer) (*Framed, error) {
+	kb := C.seb_keys{data: (*C.uint8_t)(ops.Keys.Data), offsets: (*C.uint64_t)(ops.Keys.Offsets), n: C.uint64_t(ops.Keys.N),
+		stride: C.uint32_t(ops.Keys.Stride)}
+	cuts := make([]uint64, cutCap+1)
+	var total, ncuts C.uint64_t
+	rc := C.seb_dev_seg_frame_plan(&kb, (*C.uint64_t)(ops.ValOff), (*C.uint8_t)(ops.Deleted), C.uint64_t(activeSize), C.uint64_t(limit),
+		(*C.uint64_t)(recOff), u64Ptr(cuts), C.uint64_t(cutCap), &total, &ncuts, stream)
+	if rc == C.SEB_ERR_RANGE {
+		return &Framed{Cuts: make([]uint64, uint64(ncuts))}, ErrCuts
+	}
+	if rc != 0 {
+		return nil, lastError("failed to plan the segment frame")
+	}
+	return &Framed{ImageBytes: uint64(total), Cuts: cuts[:ncuts]}, nil
+}
+
+// Frame writes the sealed records (every one with `timestamp`, the reference's time.Now().Unix()) into image
+// (ImageBytes bytes of device memory, any alignment: the pool behind its last byte, say); not synchronised.
+func Frame(ops Ops, timestamp uint64, recOff, image unsafe.Pointer, imageBytes uint64, stream unsafe.Pointer) error {
+	kb := C.seb_keys{data: (*C.uint8_t)(ops.Keys.Data), offsets: (*C.uint64_t)(ops.Keys.Offsets), n: C.uint64_t(ops.Keys.N),
+		stride: C.uint32_t(ops.Keys.Stride)}
+	if C.seb_dev_seg_frame_emit(&kb, (*C.uint8_t)(ops.Vals), (*C.uint64_t)(ops.ValOff), (*C.uint8_t)(ops.Deleted), C.uint64_t(timestamp),
+		(*C.uint64_t)(recOff), (*C.uint8_t)(image), C.uint64_t(imageBytes), stream) != 0 {
+		return lastError("failed to frame the batch")
+	}
+	return nil
+}
+
+// FrameHost is the same on the host: key i = keyData[keyOff[i]:keyOff[i+1]], value i = vals[valOff[i]:valOff[i+1]].
+// It returns the sealed image, the records' boundaries and the cuts.
+func FrameHost(keyData []byte, keyOff []uint64, vals []byte, valOff []uint64, deleted []byte, timestamp, activeSize, limit uint64) ([]byte, []uint64, []uint64, error) {
+	n := len(keyOff) - 1
+	if n < 0 {
+		n = 0
+	}
+	kb := C.seb_keys{data: bytesPtr(keyData), offsets: u64Ptr(keyOff), n: C.uint64_t(n)}
+	recOff, cuts := make([]uint64, n+1), make([]uint64, n+1)
+	var total, ncuts C.uint64_t
+	if C.seb_seg_frame_plan(&kb, u64Ptr(valOff), bytesPtr(deleted), C.uint64_t(activeSize), C.uint64_t(limit), u64Ptr(recOff), u64Ptr(cuts),
+		C.uint64_t(n), &total, &ncuts) != 0 {
+		return nil, nil, nil, lastError("failed to plan the segment frame")
+	}
+	image := make([]byte, uint64(total))
+	if C.seb_seg_frame_emit(&kb, bytesPtr(vals), u64Ptr(valOff), bytesPtr(deleted), C.uint64_t(timestamp), bytesPtr(image), total) != 0 {
+		return nil, nil, nil, lastError("failed to frame the batch")
+	}
+	return image, recOff, cuts[:ncuts], nil
+}
+
+// Compacted is what a compaction leaves: its counters, the new pool's segments, and the key count.
+type Compacted struct {
+	RecordsIn, LiveIn, Distinct, Survivors, Tombstoned, Shadowed, ImageBytes uint64
+	SegBase, SegBytes                                                        []uint64 // the new image first
+	Keys                                                                     uint64
+}
+
+// ErrCapacity is returned with Compacted's sizes and segments filled where dstCap or newRecCap is below the need
+// (ImageBytes + the bytes of the segments that stay; Survivors + restRecords + 1).
+var ErrCapacity = fmt.Errorf("a capacity is below the compaction's sizes")
+
+// Compact runs compactSegments + applyCompaction on ctx for the oldest c of the segments that devPool holds back to
+// back (segBase / segBytes, oldest first).  A bad record in one of the c segments aborts, as the reference does.  The
+// segments that stay come with their live records' offsets (restRecOff, restLive: device memory).  dstPool receives
+// the new image and those segments, newRecOff (device u64) every record's offset in it, devTable the rebuilt index.
+// See "naming the compacted file" above.
+func Compact(ctx unsafe.Pointer, devPool unsafe.Pointer, poolBytes uint64, segBase, segBytes []uint64, c uint64,
+	restRecOff, restLive unsafe.Pointer, restRecords, timestamp uint64, dstPool unsafe.Pointer, dstCap uint64,
+	devTable unsafe.Pointer, capacity uint64, newRecOff unsafe.Pointer, newRecCap uint64) (*Compacted, error) {
+	s := uint64(len(segBase))
+	out := &Compacted{SegBase: make([]uint64, s+1), SegBytes: make([]uint64, s+1)}
+	var sz C.seb_segcompact_sizes
+	var keys C.uint64_t
+	rc := C.seb_hidx_compact((*C.seb_ctx)(ctx), (*C.uint8_t)(devPool), C.uint64_t(poolBytes), u64Ptr(segBase), u64Ptr(segBytes),
+		C.uint64_t(s), C.uint64_t(c), (*C.uint64_t)(restRecOff), (*C.uint8_t)(restLive), C.uint64_t(restRecords), C.uint64_t(timestamp),
+		(*C.uint8_t)(dstPool), C.uint64_t(dstCap), devTable, C.uint64_t(capacity), (*C.uint64_t)(newRecOff), C.uint64_t(newRecCap), &sz,
+		u64Ptr(out.SegBase), u64Ptr(out.SegBytes), &keys)
+	out.RecordsIn, out.LiveIn, out.Distinct, out.Survivors = uint64(sz.records_in), uint64(sz.live_in), uint64(sz.distinct), uint64(sz.survivors)
+	out.Tombstoned, out.Shadowed, out.ImageBytes, out.Keys = uint64(sz.tombstoned), uint64(sz.shadowed), uint64(sz.image_bytes), uint64(keys)
+	if c >= 1 && c <= s {
+		out.SegBase, out.SegBytes = out.SegBase[:s-c+1], out.SegBytes[:s-c+1]
+	}
+	if rc == C.SEB_ERR_RANGE {
+		return out, ErrCapacity
+	}
+	if rc != 0 {
+		return nil, lastError("failed to compact the hash index")
+	}
+	return out, nil
+}
+
+// LogicalSize is getLogicalSize (hashindex.go:360-385): keySize + valueSize over the table's entries, tombstoned keys
+// included; the denominator of the space-amplification trigger.  It synchronises.
+func LogicalSize(table unsafe.Pointer, capacity uint64, pool unsafe.Pointer, poolBytes uint64, stream unsafe.Pointer) (uint64, error) {
+	var v C.uint64_t
+	if C.seb_dev_hidx_logical_size(table, C.uint64_t(capacity), (*C.uint8_t)(pool), C.uint64_t(poolBytes), &v, stream) != 0 {
+		return 0, lastError("failed to take the logical size")
+	}
+	return uint64(v), nil
 }

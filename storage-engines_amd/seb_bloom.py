@@ -102,6 +102,14 @@ class seb_blockids_sizes(C.Structure):
         return (self.cells, self.resident, self.misses, self.uniq, self.bad)
 
 
+class seb_segcompact_sizes(C.Structure):
+    _fields_ = [("records_in", C.c_uint64), ("live_in", C.c_uint64), ("distinct", C.c_uint64), ("survivors", C.c_uint64),
+                ("tombstoned", C.c_uint64), ("shadowed", C.c_uint64), ("image_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class seb_run(C.Structure):
     """A sorted run in the builder's input layout (the memtable lookup): host or device pointers per entry point."""
     _fields_ = [("keys", C.c_void_p), ("key_bytes", C.c_uint64), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
@@ -274,6 +282,19 @@ _SIGS = {
     "seb_dev_hidx_get": (_i, [_vp, _u64, _vp, _u64, C.POINTER(seb_keys), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_hidx_recover": (_i, [_vp, C.POINTER(_vp), C.POINTER(_u64), _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp,
                               C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "seb_seg_frame_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "seb_seg_frame_emit": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _u64, _vp, _u64]),
+    "seb_dev_seg_frame_plan": (_i, [C.POINTER(seb_keys), _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64),
+                                    _vp]),
+    "seb_dev_seg_frame_emit": (_i, [C.POINTER(seb_keys), _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "seb_seg_compact": (_i, [_vp, _u64, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _u64, C.POINTER(seb_segcompact_sizes)]),
+    "seb_dev_seg_compact_workspace_size": (_u64, [_u64]),
+    "seb_dev_seg_compact_plan": (_i, [_vp, _u64, _vp, _vp, _u64, _vp, _u64, C.POINTER(seb_segcompact_sizes), _vp]),
+    "seb_dev_seg_compact_emit": (_i, [_vp, _u64, _vp, _u64, _u64, C.POINTER(seb_segcompact_sizes), _vp, _u64, _vp, _vp, _vp]),
+    "seb_hidx_logical_size": (_i, [_vp, _u64, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "seb_dev_hidx_logical_size": (_i, [_vp, _u64, _vp, _u64, C.POINTER(_u64), _vp]),
+    "seb_hidx_compact": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _u64,
+                              C.POINTER(seb_segcompact_sizes), _vp, _vp, C.POINTER(_u64)]),
     "seb_dev_pack_residues": (_i, [C.POINTER(seb_keys), _u64, _u32, _vp, _vp]),
     "seb_dev_probe_packed": (_i, [_vp, _u64, _vp, _u64, _u32, _vp, _vp]),
     "seb_dev_probe_emit_packed": (_i, [C.POINTER(seb_keys), _vp, _u64, _u32, _vp, _vp, _vp]),
@@ -2099,6 +2120,137 @@ def dev_hidx_get(table, capacity: int, pool, pool_bytes: int, keys: seb_keys, ve
                                  _ptr(rec), _ptr(vloc), _ptr(vlen), _ptr(source), _stream(stream)))
 
 
+# ------------------------------- hash index, write side (hashindex/segment.go:61-125, hashindex.go:92-215, compaction.go)
+
+SEG_NO_LIMIT = 1 << 62  # a rotation limit no segment reaches
+
+
+def seg_frame_plan(keys, val_off, deleted=None, active_size: int = 0, limit: int = SEG_NO_LIMIT, cut_cap: int | None = None):
+    """The host half's plan of a Put / Delete batch for the hash index: (rec_off u64 of n + 1 boundaries, cuts u64,
+    image bytes).  cut_cap: the cuts' capacity (default: always enough; below the count: SebError RANGE).  An empty
+    key, a key or value of 2^32 bytes or more, keySize + valueSize >= 2^32 or offsets that decrease: SebError
+    (INVALID) naming "op I"."""
+    kb = as_keys(keys)
+    vo = np.ascontiguousarray(val_off, dtype=np.uint64)
+    de = None if deleted is None else np.ascontiguousarray(deleted, dtype=np.uint8)
+    off, total, ncuts = np.zeros(kb.n + 1, np.uint64), _u64(0), _u64(0)
+    cap = kb.n if cut_cap is None else cut_cap
+    cut = np.zeros(max(cap, 1), np.uint64)
+    check(lib().seb_seg_frame_plan(kb.ref, vo.ctypes.data, _np_ptr(de), active_size, limit, off.ctypes.data, cut.ctypes.data, cap,
+                                   C.byref(total), C.byref(ncuts)))
+    return off, cut[: ncuts.value].copy(), total.value
+
+
+def seg_frame(keys, vals, val_off, deleted=None, timestamp: int = 0, active_size: int = 0, limit: int = SEG_NO_LIMIT):
+    """The host half: the batch as segment.append's sealed records, every one with `timestamp` (a Delete with no
+    value): (image u8, rec_off u64, cuts u64)."""
+    kb, va, vo, de = _ops_host_args(keys, vals, val_off, deleted)
+    off, cuts, total = seg_frame_plan(kb, vo, de, active_size, limit)
+    image = np.zeros(max(total, 1), np.uint8)
+    check(lib().seb_seg_frame_emit(kb.ref, va.ctypes.data, vo.ctypes.data, _np_ptr(de), timestamp, image.ctypes.data, total))
+    return image[:total], off, cuts
+
+
+def dev_seg_frame_plan(keys: seb_keys, val_off, deleted, rec_off, active_size: int = 0, limit: int = SEG_NO_LIMIT,
+                       cut_cap: int | None = None, stream=None) -> tuple[int, np.ndarray]:
+    """Device form: rec_off (n + 1 u64, a 64-bit tensor) is written; synchronises and returns (image bytes, cuts u64 on
+    the host)."""
+    if keys.n and (rec_off is None or _nbytes(rec_off) < 8 * (keys.n + 1)):
+        raise ValueError(f"rec_off holds fewer than {keys.n + 1} offsets")
+    total, ncuts = _u64(0), _u64(0)
+    cap = keys.n if cut_cap is None else cut_cap
+    cut = np.zeros(max(cap, 1), np.uint64)
+    check(lib().seb_dev_seg_frame_plan(C.byref(keys), _ptr(val_off), _ptr(deleted), active_size, limit, _ptr(rec_off),
+                                       cut.ctypes.data, cap, C.byref(total), C.byref(ncuts), _stream(stream)))
+    return total.value, cut[: ncuts.value].copy()
+
+
+def dev_seg_frame_emit(keys: seb_keys, vals, val_off, deleted, timestamp: int, rec_off, image, image_bytes: int | None = None,
+                       stream=None) -> None:
+    """Device form: the sealed image into `image` (u8 tensor or view, any alignment); rec_off and image_bytes as
+    dev_seg_frame_plan left them.  Not synchronised."""
+    total = (_nbytes(image) if image is not None else 0) if image_bytes is None else image_bytes
+    if total and image is not None and _nbytes(image) < total:
+        raise ValueError(f"image holds {_nbytes(image)} bytes, the plan needs {total}")
+    check(lib().seb_dev_seg_frame_emit(C.byref(keys), _ptr(vals), _ptr(val_off), _ptr(deleted), timestamp, _ptr(rec_off),
+                                       _ptr(image), total, _stream(stream)))
+
+
+def seg_compact(pool, rec_off, live, timestamp: int, caps: tuple[int, int] | None = None):
+    """compactSegments on the host over the live records (live None: all) of the chosen segments: (image u8,
+    out_rec_off u64 of survivors + 1, sizes dict).  caps: (image bytes, offsets) instead of the sizing call's."""
+    pool, rec_off = _bytes_arg(pool), np.ascontiguousarray(rec_off, dtype=np.uint64)
+    lv = None if live is None else np.ascontiguousarray(live, dtype=np.uint8)
+    sz = seb_segcompact_sizes()
+    if caps is None:
+        check(lib().seb_seg_compact(_np_ptr(pool), pool.size, _np_ptr(rec_off), _np_ptr(lv), rec_off.size, timestamp, None, 0, None,
+                                    0, C.byref(sz)))
+        caps = (sz.image_bytes, sz.survivors + 1)
+    image, out = np.zeros(max(caps[0], 1), np.uint8), np.zeros(max(caps[1], 1), np.uint64)
+    rc = lib().seb_seg_compact(_np_ptr(pool), pool.size, _np_ptr(rec_off), _np_ptr(lv), rec_off.size, timestamp, image.ctypes.data,
+                               caps[0], out.ctypes.data, caps[1], C.byref(sz))
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.sizes = sz.as_dict()
+        raise err
+    return image[: sz.image_bytes], out[: sz.survivors + 1], sz.as_dict()
+
+
+def segs_compact(segments, num_segments: int, timestamp: int):
+    """compactSegments of the oldest num_segments segment images on the host, as the reference runs it: scan, verify,
+    and a record that fails its CRC in one of them aborts the compaction (SebError INVALID naming segment and record);
+    a short tail is dropped silently.  Returns seg_compact's triple."""
+    pool, rec_off, first, base, size, _ = segs_scan(list(segments)[:num_segments])
+    _, valid, _, live = seg_verify(pool, rec_off, first, base, size)
+    for s in range(num_segments):
+        if int(valid[s]) < int(first[s + 1]) - int(first[s]):
+            raise SebError(-1, f"segs_compact: segment {s}: record {int(valid[s])} fails its CRC: the compaction is aborted")
+    return seg_compact(pool, rec_off, live, timestamp)
+
+
+def hidx_logical_size(pool, rec_off, live=None) -> int:
+    """getLogicalSize on the host: keySize + valueSize over the index of the live records, tombstones included."""
+    pool, rec_off = _bytes_arg(pool), np.ascontiguousarray(rec_off, dtype=np.uint64)
+    lv = None if live is None else np.ascontiguousarray(live, dtype=np.uint8)
+    out = _u64(0)
+    check(lib().seb_hidx_logical_size(_np_ptr(pool), pool.size, _np_ptr(rec_off), _np_ptr(lv), rec_off.size, C.byref(out)))
+    return out.value
+
+
+def dev_seg_compact_workspace_size(num_records: int) -> int:
+    return lib().seb_dev_seg_compact_workspace_size(num_records)
+
+
+def dev_seg_compact_plan(pool, pool_bytes: int, rec_off, live, n: int, ws, ws_bytes: int | None = None,
+                         stream=None) -> seb_segcompact_sizes:
+    """Device form: the scratch table, the survivors' marks and their scan into `ws`; synchronises and returns the sizes."""
+    sz = seb_segcompact_sizes()
+    check(lib().seb_dev_seg_compact_plan(_ptr(pool), pool_bytes, _ptr(rec_off), _ptr(live), n, _ptr(ws),
+                                         (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes, C.byref(sz),
+                                         _stream(stream)))
+    return sz
+
+
+def dev_seg_compact_emit(pool, pool_bytes: int, rec_off, n: int, timestamp: int, sizes: seb_segcompact_sizes, ws, image,
+                         out_rec_off, ws_bytes: int | None = None, stream=None) -> None:
+    """Device form: the survivors into `image` (any alignment) and their offsets into out_rec_off (survivors + 1 u64).
+    Not synchronised."""
+    if image is not None and _nbytes(image) < sizes.image_bytes:
+        raise ValueError(f"image holds {_nbytes(image)} bytes, the plan needs {sizes.image_bytes}")
+    if out_rec_off is None or _nbytes(out_rec_off) < 8 * (sizes.survivors + 1):
+        raise ValueError(f"out_rec_off holds fewer than {sizes.survivors + 1} offsets")
+    check(lib().seb_dev_seg_compact_emit(_ptr(pool), pool_bytes, _ptr(rec_off), n, timestamp, C.byref(sizes), _ptr(ws),
+                                         (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes, _ptr(image),
+                                         _ptr(out_rec_off), _stream(stream)))
+
+
+def dev_hidx_logical_size(table, capacity: int, pool, pool_bytes: int, stream=None) -> int:
+    """getLogicalSize over the table; synchronises."""
+    out = _u64(0)
+    check(lib().seb_dev_hidx_logical_size(_ptr(table), capacity, _ptr(pool), pool_bytes, C.byref(out), _stream(stream)))
+    return out.value
+
+
 def _ctx_hidx_recover(self, segments, dev_pool, dev_table, capacity: int, pool_cap: int | None = None):
     """seb_hidx_recover: the segment images (host, oldest first) into the device pool and table.  Returns a dict:
     valid, size_after, short_tail, cut (per segment), records, live_records, distinct.  SebError (RANGE) carries the
@@ -2126,6 +2278,35 @@ def _ctx_hidx_recover(self, segments, dev_pool, dev_table, capacity: int, pool_c
 Ctx.hidx_recover = _ctx_hidx_recover
 
 
+def _ctx_hidx_compact(self, dev_pool, pool_bytes: int, seg_base, seg_bytes, num_compact: int, rest_rec_off, rest_live,
+                      rest_records: int, timestamp: int, dst_pool, dev_table, capacity: int, new_rec_off,
+                      dst_cap: int | None = None):
+    """seb_hidx_compact: the oldest num_compact segments of the device pool compacted into the front of dst_pool, the
+    others copied behind, the table rebuilt.  Returns a dict: sizes, seg_base, seg_bytes (of the new pool), distinct,
+    pool_bytes, records (the entries of new_rec_off).  SebError (RANGE) carries sizes / seg_base / seg_bytes as
+    `.compacted` where a capacity is below the need."""
+    base, size = (np.ascontiguousarray(a, dtype=np.uint64) for a in (seg_base, seg_bytes))
+    s = base.size
+    out = s - num_compact + 1
+    nbase, nsize = np.zeros(max(out, 1), np.uint64), np.zeros(max(out, 1), np.uint64)
+    sz, distinct = seb_segcompact_sizes(), _u64(0)
+    cap = (_nbytes(dst_pool) if dst_pool is not None else 0) if dst_cap is None else dst_cap
+    rc = lib().seb_hidx_compact(self._p, _ptr(dev_pool), pool_bytes, _np_ptr(base), _np_ptr(size), s, num_compact,
+                                _ptr(rest_rec_off), _ptr(rest_live), rest_records, timestamp, _ptr(dst_pool), cap, _ptr(dev_table),
+                                capacity, _ptr(new_rec_off), _nbytes(new_rec_off) // 8 if new_rec_off is not None else 0,
+                                C.byref(sz), _np_ptr(nbase), _np_ptr(nsize), C.byref(distinct))
+    got = dict(sizes=sz.as_dict(), seg_base=nbase[:out], seg_bytes=nsize[:out])
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.compacted = got
+        raise err
+    got.update(distinct=distinct.value, pool_bytes=int(nbase[out - 1] + nsize[out - 1]), records=sz.survivors + rest_records)
+    return got
+
+
+Ctx.hidx_compact = _ctx_hidx_compact
+
+
 class HashIndex:
     """The read side of the reference's hash index on one device: the segment pool and the key table live in device
     memory.  recover(segments) is hashindex's recover(); get_batch(keys) is HashIndex.Get for a batch, ending in the
@@ -2138,6 +2319,8 @@ class HashIndex:
         self.pool = self.table = None
         self.pool_bytes = self.capacity = self.count = 0
         self.segment_sizes = np.zeros(0, np.uint64)
+        self.segment_limit = SEG_NO_LIMIT  # put_batch's rotation limit (SegmentSizeBytes)
+        self._seg_bytes = []  # the bytes each segment takes in the pool (a cut segment keeps its image's)
         self._images, self._runs = None, []  # the recovered images and every insert's (rec_off, live, n) device tensors:
                                              # what a rebuild into a larger table needs
 
@@ -2168,10 +2351,11 @@ class HashIndex:
                 cap = e.recovered["live_records"]  # cannot fill again
         self.count = got["distinct"]
         self.segment_sizes = got["size_after"].copy()
+        self._seg_bytes = [a.size for a in imgs]
         self._images, self._runs = imgs, []  # a rebuild into a larger table scans and verifies them again (_insert_all)
         return got
 
-    def _insert_all(self):
+    def _materialize(self):
         import torch
         if self._images is not None:  # the recovered segments' records, as the device arrays an insert takes
             dev = self.pool.device
@@ -2180,6 +2364,9 @@ class HashIndex:
             self._runs.insert(0, (torch.from_numpy(rec_off.view(np.int64).copy()).to(dev), torch.from_numpy(live.copy()).to(dev),
                                   rec_off.size))
             self._images = None
+
+    def _insert_all(self):
+        self._materialize()
         dev_hidx_clear(self.table, self.capacity)
         for rec_off, live, n in self._runs:
             if n:
@@ -2198,6 +2385,8 @@ class HashIndex:
         n = rec_off.size
         self.pool[self.pool_bytes: self.pool_bytes + buf.size] = torch.from_numpy(buf.copy()).to(dev)
         self.pool_bytes += buf.size
+        if self._seg_bytes:
+            self._seg_bytes[-1] += buf.size
         if n == 0:
             return 0
         d_off = torch.from_numpy(rec_off.view(np.int64).copy()).to(dev)
@@ -2248,3 +2437,110 @@ class HashIndex:
                             pool_bytes=self.pool_bytes)
         torch.cuda.synchronize(dev)
         return status.cpu().numpy(), out_off.cpu().numpy().view(np.uint64), out_vals.cpu().numpy()[: sz.val_bytes]
+
+
+    # ------------------------------------------------ the write side
+
+    def _count_or_grow(self, added: int) -> None:
+        import torch
+        try:
+            self.count = dev_hidx_count(self.table, self.capacity)[0]
+        except SebError as e:
+            if e.code != -4:
+                raise
+            self.capacity = max(2 * self.capacity, self.count + added)
+            self.table = torch.empty(dev_hidx_table_bytes(self.capacity), dtype=torch.uint8, device=self.pool.device)
+            self.count = self._insert_all()
+
+    def put_batch(self, keys, vals, val_off, deleted=None, timestamp: int = 0):
+        """HashIndex.Put / Delete for a batch (ops as seg_frame takes them, host memory): framed and sealed on the device
+        straight behind the pool, verified, inserted.  Rotation at `segment_limit`.  Returns (image u8, rec_off u64 of
+        n + 1 offsets within the image, cuts u64): the engine appends image[:rec_off[cuts[0]]] to its active file and
+        opens a new file at every cut."""
+        import torch
+        kb, va, vo, de = _ops_host_args(keys, vals, val_off, deleted)
+        n = kb.n
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        dev = torch.device("cuda", self.device)
+        if self.pool is None:
+            self.pool = torch.zeros(16, dtype=torch.uint8, device=dev)
+            self.capacity = max(n, 16)
+            self.table = torch.zeros(dev_hidx_table_bytes(self.capacity), dtype=torch.uint8, device=dev)
+        if not self._seg_bytes:
+            self._seg_bytes, self.segment_sizes = [0], np.zeros(1, np.uint64)
+        data = torch.from_numpy(kb.data.reshape(-1).copy() if kb.data.size else np.zeros(1, np.uint8)).to(dev)
+        if kb.offsets is not None:
+            dk = dev_keys(data, torch.from_numpy(kb.offsets.view(np.int64).copy()).to(dev))
+        else:
+            dk = dev_keys(data, n=n, stride=kb.stride)
+        d_vals = torch.from_numpy(va.copy() if va.size else np.zeros(1, np.uint8)).to(dev)
+        d_voff = torch.from_numpy(vo.view(np.int64).copy()).to(dev)
+        d_del = None if de is None else torch.from_numpy(de.copy()).to(dev)
+        d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        total, cuts = dev_seg_frame_plan(dk, d_voff, d_del, d_off, int(self._seg_bytes[-1]), self.segment_limit)
+        if self.pool_bytes + total > self.pool.numel():
+            grown = torch.zeros(max(2 * self.pool.numel(), self.pool_bytes + total), dtype=torch.uint8, device=dev)
+            grown[: self.pool_bytes] = self.pool[: self.pool_bytes]
+            self.pool = grown
+        at = self.pool_bytes
+        image = self.pool[at: at + total]
+        dev_seg_frame_emit(dk, d_vals, d_voff, d_del, timestamp, d_off, image, total)
+        self.pool_bytes += total
+        p_off = (d_off[:n] + at).contiguous()
+        d_first = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        ok = torch.empty(n, dtype=torch.uint8, device=dev)
+        live = torch.empty(n, dtype=torch.uint8, device=dev)
+        valid = torch.empty(1, dtype=torch.int64, device=dev)
+        dev_seg_verify(self.pool, self.pool_bytes, p_off, n, d_first, 1, ok, valid, live)
+        self._materialize()
+        self._runs.append((p_off, live, n))
+        dev_hidx_insert(self.table, self.capacity, self.pool, self.pool_bytes, p_off, live, n)
+        self._count_or_grow(n)
+        rec_off = d_off.cpu().numpy().view(np.uint64)
+        edges = [0] + [int(rec_off[int(c)]) for c in cuts] + [total]
+        sizes = [edges[i + 1] - edges[i] for i in range(len(edges) - 1)]
+        self._seg_bytes[-1] += sizes[0]
+        self._seg_bytes += sizes[1:]
+        self.segment_sizes = np.concatenate([self.segment_sizes, np.zeros(len(sizes) - 1, np.uint64)])
+        self.segment_sizes[len(self.segment_sizes) - len(sizes):] += np.array(sizes, np.uint64)
+        return image.cpu().numpy(), rec_off, cuts
+
+    def compact(self, num_segments: int, timestamp: int = 0) -> dict:
+        """compactSegments + applyCompaction for the oldest num_segments segments: their live records' survivors
+        become one new segment at the front of a new pool, the other segments follow it unchanged, and the table
+        is rebuilt from everything (linear probing has no delete).  Every Get answers as before; `count` drops by
+        the keys whose latest record was a tombstone in a compacted segment.  Returns the compaction's sizes."""
+        import torch
+        c = num_segments
+        if self.pool is None or not 1 <= c <= len(self._seg_bytes):
+            raise ValueError(f"compact({c}) of {len(self._seg_bytes)} segments")
+        self._materialize()
+        dev = self.pool.device
+        edge = int(sum(int(b) for b in self._seg_bytes[:c]))  # where the first segment that stays begins
+        runs = [r for r in self._runs if r[2]]
+        rec = torch.cat([r[0][: r[2]] for r in runs]) if runs else torch.zeros(0, dtype=torch.int64, device=dev)
+        live = torch.cat([r[1][: r[2]] for r in runs]) if runs else torch.zeros(0, dtype=torch.uint8, device=dev)
+        n_c = int((rec < edge).sum())  # the runs lie in pool order: the compacted segments' records come first
+        head_off, head_live = rec[:n_c].contiguous(), live[:n_c].contiguous()
+        ws = torch.empty(max(dev_seg_compact_workspace_size(n_c), 16), dtype=torch.uint8, device=dev)
+        sz = dev_seg_compact_plan(self.pool, self.pool_bytes, head_off if n_c else None, head_live if n_c else None, n_c, ws)
+        rest = self.pool_bytes - edge
+        total = sz.image_bytes + rest
+        pool = torch.zeros(max(total + self.pool.numel() - self.pool_bytes, 16), dtype=torch.uint8, device=dev)
+        out_off = torch.empty(sz.survivors + 1, dtype=torch.int64, device=dev)
+        dev_seg_compact_emit(self.pool, self.pool_bytes, head_off if n_c else None, n_c, timestamp, sz, ws,
+                             pool if sz.image_bytes else None, out_off)
+        pool[sz.image_bytes: total] = self.pool[edge: self.pool_bytes]
+        rest_off = (rec[n_c:] - edge + sz.image_bytes).contiguous()
+        ones = torch.ones(sz.survivors, dtype=torch.uint8, device=dev)
+        self.pool, self.pool_bytes = pool, total
+        self._runs = [(out_off[: sz.survivors].contiguous(), ones, sz.survivors), (rest_off, live[n_c:].contiguous(), rec.numel() - n_c)]
+        self._seg_bytes = [sz.image_bytes] + list(self._seg_bytes[c:])
+        self.segment_sizes = np.concatenate([np.array([sz.image_bytes], np.uint64), self.segment_sizes[c:]])
+        self.count = self._insert_all()
+        return sz.as_dict()
+
+    def logical_size(self) -> int:
+        """getLogicalSize: keySize + valueSize over the index, tombstoned keys included."""
+        return dev_hidx_logical_size(self.table, self.capacity, self.pool, self.pool_bytes)
