@@ -1366,6 +1366,94 @@ int seb_hidx_compact(seb_ctx *ctx, const uint8_t *dev_pool, uint64_t pool_bytes,
                      uint64_t new_rec_cap, seb_segcompact_sizes *sizes, uint64_t *new_seg_base, uint64_t *new_seg_bytes,
                      uint64_t *distinct);
 
+/* ------------- B-tree, read side: a page-file image checked, Get for a key batch ---- */
+/* The reference's third engine (btree/) is a page-based B+-tree in one file.  This group is its read side: what
+ * readMetadata (btree/pager.go:142-164) makes of the file, a structural check of every page, and what Get
+ * (btree/btree.go:232-280) answers from the pages, for a key batch.  Range scans, the write side (Put, splits, Delete,
+ * merges), the WAL's replay and the pager's cache stay with the caller, who hands over the image that Sync wrote, with
+ * any WAL already applied.
+ *
+ * Layout (btree/page.go:9-44): page p at byte p * SEB_BT_PAGE_BYTES; every integer big-endian.  Page 0: magic,
+ * RootPageID, NumPages, FreeListPtr at bytes 0, 4, 8, 12.  A page: [type u8: 1 internal, 2 leaf][numCells u16]
+ * [rightPtr u32][freePtr u16][version u8], then a directory of u16 cell offsets IN KEY ORDER; the cells grow down from
+ * the page end and deleted or updated ones leave dead bytes behind, so only the directory is sorted.  Version 0 or 1
+ * is V1 (leaf cell: ks u16, vs u16, key, value; internal cell: ks u16, child u32, key); any other version byte is V2
+ * (the sizes are varints of btree/varint.go:34-85; a value above 0xFFFF is an error).  An internal page's rightPtr is
+ * its LEFTMOST child (keys below every cell); a leaf's is the next leaf, or 0.
+ *
+ * seb_bt_open is readMetadata: SEB_ERR_INVALID where the reference gives ErrInvalidDatabase (fewer than 4096 bytes, a
+ * wrong magic).  meta->num_pages = min(NumPages, image_bytes / 4096) is the bound EVERY later page access is held to:
+ * readPage's "out of bounds" and a file shorter than its header claims.
+ *
+ * seb_bt_check, the pass an open should be followed by.  kind[p] for p >= 1 (page 0 is SEB_BT_PAGE_BAD and is not
+ * counted): a page is good, and kind[p] its type, when the type is 1 or 2; the directory fits (10 + 2 * numCells <=
+ * 4096); every cell parses by CellAt's rules without a byte read outside the page; the directory's keys increase
+ * strictly; an internal page's children and rightPtr lie in [1, num_pages); a leaf's rightPtr is 0 or in that range.
+ * level[p] = the page's distance from the root over good internal pages, SEB_BT_NO_LEVEL where it has none within
+ * SEB_BT_MAX_DEPTH pages (the root itself has level 0 whatever it holds, if its id lies in [1, num_pages)).  stats:
+ * see the struct.  kind, level and stats are nullable.
+ *
+ * seb_bt_get.  Per key: SEB_GET_FOUND with leaf = the leaf reached, pos = the matched directory index, vloc = the
+ * value's byte offset within the image (page * 4096 + cell offset + header + keySize), vlen = valueSize (0 is still
+ * found); SEB_GET_MISS with leaf and pos = searchCell's insertion point (what Iterator.seek computes), vloc = vlen =
+ * 0; SEB_GET_ERROR with leaf = the page it arose at, pos = vloc = vlen = 0.  The (status, vloc, vlen) arrays are the
+ * ones seb_dev_get_values_* takes, with the image as its `pool`, source = 1 and num_runs = 0.
+ * The bisection is fixed so that host and device agree on any bytes: a leaf is searchCell (btree/page.go:451-473)
+ * literally; an internal page takes lo = 0, hi = n, mid = (lo + hi) / 2, key >= cell[mid].key ? lo = mid + 1 : hi =
+ * mid, and descends to rightPtr when lo == 0, else to cell[lo - 1].child; on every page the check calls good that is
+ * findChild's linear scan (btree/btree.go:200-229).
+ * SEB_GET_ERROR: an empty key (ErrKeyEmpty; leaf = SEB_BT_NO_PAGE); a page id outside [1, num_pages) (leaf = that id);
+ * and the DEPARTURES from the reference, which there walk garbage, panic or skip: a page whose type is neither 1 nor
+ * 2 (the reference treats it as internal); a touched cell that fails to parse, or whose directory entry or V2 child id
+ * lies past the page end (searchCell answers "not found", findChild skips the cell with `continue`, getCellOffset and
+ * the child read panic); an internal page as the SEB_BT_MAX_DEPTH-th page of the walk (leaf = that page), which is
+ * how a cycle ends (the reference loops for ever).
+ * A key longer than 65,535 bytes is no stored key: it is compared by its first 65,536 bytes, which orders it exactly.
+ *
+ * Host forms: host memory, keys in every seb_keys layout; they are the reference for the device forms and what a
+ * caller without a GPU uses.  SEB_ERR_INVALID: a NULL required pointer, meta->num_pages pages that do not fit
+ * image_bytes, key offsets that decrease.
+ * Device forms: device pointers (key offsets and vloc 8-byte aligned; leaf, pos and vlen 4-byte aligned; the IMAGE,
+ * keys, kind, level, status and source at any byte alignment); meta and stats are HOST memory.  SEB_ERR_INVALID and
+ * nothing launched: a NULL required pointer, a misaligned one, num_pages pages that do not fit image_bytes, more than
+ * 2^31 pages (8 TiB).
+ * seb_dev_bt_check SYNCHRONISES (one read-back per level round and one for the counts); seb_dev_bt_get does not;
+ * source[i] (nullable) = 1 for a FOUND key, else 0.  Bounds, whatever the image holds: every page id is tested against
+ * num_pages before a byte of the page is read, every offset against 4096 before it is used, both loops of the walk
+ * are counted, and nothing is written outside the keys->n elements of the outputs (num_pages of kind and level). */
+#define SEB_BT_PAGE_BYTES 4096u
+#define SEB_BT_MAGIC 0x42545245u
+#define SEB_BT_MAX_DEPTH 32u
+#define SEB_BT_NO_PAGE UINT32_MAX
+#define SEB_BT_NO_LEVEL 0xFFu
+enum seb_bt_page_kind { SEB_BT_PAGE_BAD = 0, SEB_BT_PAGE_INTERNAL = 1, SEB_BT_PAGE_LEAF = 2 };
+typedef struct seb_bt_meta {
+    uint32_t root, header_pages; /* RootPageID, the header's NumPages */
+    uint32_t free_list, num_pages; /* FreeListPtr, min(NumPages, image_bytes / 4096) */
+} seb_bt_meta;
+typedef struct seb_bt_stats {
+    uint64_t leaves, internals, bad;                   /* pages [1, num_pages) by kind */
+    uint64_t reach_leaves, reach_internals, reach_bad; /* those that have a level */
+    uint64_t keys;           /* the cells on reachable good leaves: the key count Stats cannot give after a reopen */
+    uint32_t depth, uniform; /* the levels that hold a page (0: the root lies outside); 1 iff every reachable good leaf
+                              * sits at one level */
+} seb_bt_stats;
+int seb_bt_open(const uint8_t *image, uint64_t image_bytes, seb_bt_meta *meta);
+int seb_bt_check(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, uint8_t *kind, uint8_t *level,
+                 seb_bt_stats *stats);
+int seb_bt_get(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const seb_keys *keys, uint8_t *status,
+               uint32_t *leaf, uint32_t *pos, uint64_t *vloc, uint32_t *vlen);
+int seb_dev_bt_check(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, uint8_t *kind, uint8_t *level,
+                     seb_bt_stats *stats, void *stream);
+int seb_dev_bt_get(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const seb_keys *keys, uint8_t *status,
+                   uint32_t *leaf, uint32_t *pos, uint64_t *vloc, uint32_t *vlen, uint8_t *source, void *stream);
+/* open, upload, check on a context; synchronous.  image: the file in HOST memory; dev_image (DEVICE memory of cap >=
+ * meta->num_pages * 4096 bytes) receives its pages, dev_kind / dev_level (DEVICE, num_pages bytes each, nullable) the
+ * check's arrays; *meta and *stats (nullable) are filled on the host.  SEB_ERR_INVALID as seb_bt_open; SEB_ERR_RANGE:
+ * cap is below the pages' bytes (*meta is filled, nothing is uploaded). */
+int seb_bt_load(seb_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *dev_image, uint64_t cap, uint8_t *dev_kind,
+                uint8_t *dev_level, seb_bt_meta *meta, seb_bt_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

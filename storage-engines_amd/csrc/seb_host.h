@@ -27,6 +27,10 @@
 //                     dependency; seb_hashwrite.h)
 //   seb_hashwrite.hip its kernels (the seal: k_seg_crc's seal mode in seb_hashindex.hip; what both share: seb_hidx_dev.h)
 //   seb_hidx.cpp      the hash index's entry points, seb_hidx_recover and seb_hidx_compact
+//   seb_btree.h      the B-tree's page codec, page rules and walk: one text for the host half and the kernels
+//   seb_btree.cpp    the host half of the B-tree's read side: open, check, Get (no HIP dependency)
+//   seb_btree.hip    its kernels: the page check, the level rounds, the counts, Get
+//   seb_bt.cpp       the B-tree's entry points and seb_bt_load
 #pragma once
 #include <hip/hip_runtime.h>
 

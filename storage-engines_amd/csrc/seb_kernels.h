@@ -444,6 +444,17 @@ hipError_t launch_offsets_shift(const uint64_t *src, uint64_t n, uint64_t sub, u
 hipError_t launch_hidx_logical(const void *table, uint64_t capacity, const uint8_t *pool, uint64_t pool_bytes,
                                uint64_t *sum_dev, uint64_t *sum_host, hipStream_t s);
 
+// The B-tree's read side (seb_btree.hip).  The check's workspace: bt_check_ws_bytes(num_pages) bytes,
+// 16-byte aligned.  launch_bt_check synchronises the stream (a read-back per level round, one for the counts) and
+// fills *stats_host; kind and level are nullable.  launch_bt_get: leaf, pos, vloc, vlen and source are nullable;
+// nothing outside the kb.n elements of each is written.
+struct BtStats;
+uint64_t bt_check_ws_bytes(uint32_t num_pages);
+hipError_t launch_bt_check(const uint8_t *image, uint32_t num_pages, uint32_t root, uint8_t *kind, uint8_t *level, void *ws,
+                           BtStats *stats_host, hipStream_t s);
+hipError_t launch_bt_get(const uint8_t *image, uint32_t num_pages, uint32_t root, const KeyBatch &kb, uint8_t *status,
+                         uint32_t *leaf, uint32_t *pos, uint64_t *vloc, uint32_t *vlen, uint8_t *source, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).

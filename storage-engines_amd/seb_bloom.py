@@ -110,6 +110,22 @@ class seb_segcompact_sizes(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class seb_bt_meta(C.Structure):
+    _fields_ = [("root", C.c_uint32), ("header_pages", C.c_uint32), ("free_list", C.c_uint32), ("num_pages", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class seb_bt_stats(C.Structure):
+    _fields_ = [("leaves", C.c_uint64), ("internals", C.c_uint64), ("bad", C.c_uint64), ("reach_leaves", C.c_uint64),
+                ("reach_internals", C.c_uint64), ("reach_bad", C.c_uint64), ("keys", C.c_uint64), ("depth", C.c_uint32),
+                ("uniform", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class seb_run(C.Structure):
     """A sorted run in the builder's input layout (the memtable lookup): host or device pointers per entry point."""
     _fields_ = [("keys", C.c_void_p), ("key_bytes", C.c_uint64), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
@@ -295,6 +311,12 @@ _SIGS = {
     "seb_dev_hidx_logical_size": (_i, [_vp, _u64, _vp, _u64, C.POINTER(_u64), _vp]),
     "seb_hidx_compact": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _u64,
                               C.POINTER(seb_segcompact_sizes), _vp, _vp, C.POINTER(_u64)]),
+    "seb_bt_open": (_i, [_vp, _u64, C.POINTER(seb_bt_meta)]),
+    "seb_bt_check": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, _vp, C.POINTER(seb_bt_stats)]),
+    "seb_bt_get": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), C.POINTER(seb_keys), _vp, _vp, _vp, _vp, _vp]),
+    "seb_dev_bt_check": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, _vp, C.POINTER(seb_bt_stats), _vp]),
+    "seb_dev_bt_get": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), C.POINTER(seb_keys), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seb_bt_load": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.POINTER(seb_bt_meta), C.POINTER(seb_bt_stats)]),
     "seb_dev_pack_residues": (_i, [C.POINTER(seb_keys), _u64, _u32, _vp, _vp]),
     "seb_dev_probe_packed": (_i, [_vp, _u64, _vp, _u64, _u32, _vp, _vp]),
     "seb_dev_probe_emit_packed": (_i, [C.POINTER(seb_keys), _vp, _u64, _u32, _vp, _vp, _vp]),
@@ -317,6 +339,9 @@ GET_MISS, GET_FOUND, GET_ERROR = range(3)
 MEM_NONE, MEM_FOUND, MEM_TOMBSTONE = range(3)  # seb_mem_status
 MEM_MAX_RUNS = 8           # SEB_MEM_MAX_RUNS
 MEM_NO_ENTRY = 2**32 - 1   # SEB_MEM_NO_ENTRY
+BT_PAGE_BYTES, BT_MAX_DEPTH = 4096, 32               # SEB_BT_PAGE_BYTES, SEB_BT_MAX_DEPTH
+BT_NO_PAGE, BT_NO_LEVEL = 2**32 - 1, 0xFF            # SEB_BT_NO_PAGE, SEB_BT_NO_LEVEL
+BT_PAGE_BAD, BT_PAGE_INTERNAL, BT_PAGE_LEAF = range(3)  # seb_bt_page_kind
 
 
 def build_library() -> str:
@@ -2544,3 +2569,138 @@ class HashIndex:
     def logical_size(self) -> int:
         """getLogicalSize: keySize + valueSize over the index, tombstoned keys included."""
         return dev_hidx_logical_size(self.table, self.capacity, self.pool, self.pool_bytes)
+
+
+# ------------------------------- B-tree, read side: a page-file image checked, Get of a key batch (btree/)
+
+def bt_open(image) -> seb_bt_meta:
+    """readMetadata (btree/pager.go:142-164) of a page-file image on the host: the seb_bt_meta every other call takes
+    (.root, .header_pages, .free_list, .num_pages = min(NumPages, the image's whole pages)).  SebError (INVALID) where
+    the reference gives ErrInvalidDatabase."""
+    img = _bytes_arg(image)
+    meta = seb_bt_meta()
+    check(lib().seb_bt_open(_np_ptr(img), img.size, C.byref(meta)))
+    return meta
+
+
+def bt_check(image, meta: seb_bt_meta):
+    """The structural pass on the host: (kind u8, level u8, stats dict), one kind and one level per page."""
+    img = _bytes_arg(image)
+    kind, level = np.zeros(meta.num_pages, np.uint8), np.zeros(meta.num_pages, np.uint8)
+    st = seb_bt_stats()
+    check(lib().seb_bt_check(_np_ptr(img), img.size, C.byref(meta), _np_ptr(kind), _np_ptr(level), C.byref(st)))
+    return kind, level, st.as_dict()
+
+
+def bt_get(image, meta: seb_bt_meta, keys):
+    """BTree.Get for a key batch on the host: (status u8, leaf u32, pos u32, vloc u64, vlen u32).  The reference for
+    dev_bt_get."""
+    img = _bytes_arg(image)
+    kb = as_keys(keys)
+    n = kb.n
+    status, leaf, pos = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    vloc, vlen = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    check(lib().seb_bt_get(_np_ptr(img), img.size, C.byref(meta), kb.ref, _np_ptr(status), _np_ptr(leaf), _np_ptr(pos),
+                           _np_ptr(vloc), _np_ptr(vlen)))
+    return status, leaf, pos, vloc, vlen
+
+
+def dev_bt_check(image, image_bytes: int, meta: seb_bt_meta, kind=None, level=None, stream=None) -> dict:
+    """The structural pass on a device image: kind / level (u8 tensors of meta.num_pages, nullable) are filled,
+    the stats come back as a dict.  Synchronises."""
+    for name, t in (("kind", kind), ("level", level)):
+        if t is not None and _nbytes(t) < meta.num_pages:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, the image has {meta.num_pages} pages")
+    st = seb_bt_stats()
+    check(lib().seb_dev_bt_check(_ptr(image), image_bytes, C.byref(meta), _ptr(kind), _ptr(level), C.byref(st), _stream(stream)))
+    return st.as_dict()
+
+
+def dev_bt_get(image, image_bytes: int, meta: seb_bt_meta, keys: seb_keys, status, leaf=None, pos=None, vloc=None, vlen=None,
+               source=None, stream=None) -> None:
+    """BTree.Get for a device key batch: status (u8), leaf / pos (u32), vloc (u64), vlen (u32), source (u8), each of
+    keys.n elements; all but status nullable.  Not synchronised."""
+    n = keys.n
+    for name, t, size in (("status", status, n), ("leaf", leaf, 4 * n), ("pos", pos, 4 * n), ("vloc", vloc, 8 * n),
+                          ("vlen", vlen, 4 * n), ("source", source, n)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {n} keys need {size}")
+    check(lib().seb_dev_bt_get(_ptr(image), image_bytes, C.byref(meta), C.byref(keys), _ptr(status), _ptr(leaf), _ptr(pos),
+                               _ptr(vloc), _ptr(vlen), _ptr(source), _stream(stream)))
+
+
+def _ctx_bt_load(self, image, dev_image, dev_kind=None, dev_level=None, cap: int | None = None):
+    """seb_bt_load: a host image opened, uploaded into dev_image and checked.  Returns (meta, stats dict)."""
+    img = _bytes_arg(image)
+    meta, st = seb_bt_meta(), seb_bt_stats()
+    cap = (_nbytes(dev_image) if dev_image is not None else 0) if cap is None else cap
+    check(lib().seb_bt_load(self._p, _np_ptr(img), img.size, _ptr(dev_image), cap, _ptr(dev_kind), _ptr(dev_level),
+                            C.byref(meta), C.byref(st)))
+    return meta, st.as_dict()
+
+
+Ctx.bt_load = _ctx_bt_load
+
+
+class BTreeImage:
+    """The read side of the reference's B-tree on one device: the page-file image lives in device memory.
+    open(image) is readMetadata + upload + the structural check; check() runs the check again; get_batch(keys) is
+    BTree.Get for a batch, ending in the values gather (dev_get_values_*) with the image as its pool."""
+
+    def __init__(self, device: int = 0):
+        self._ctx = Ctx(device)
+        self.device = device
+        self.image = self.kind = self.level = self.meta = None
+        self.image_bytes = 0
+        self.stats = {}
+
+    def close(self):
+        self._ctx.close()
+        self.image = self.kind = self.level = None
+
+    def open(self, image) -> dict:
+        """The file's bytes (what Sync wrote, any WAL already applied).  Returns the check's stats; `meta`, `kind`
+        and `level` (device tensors, one byte per page) are set."""
+        import torch
+        img = _bytes_arg(image)
+        dev = torch.device("cuda", self.device)
+        pages = img.size // BT_PAGE_BYTES
+        self.image = torch.empty(max(pages * BT_PAGE_BYTES, 16), dtype=torch.uint8, device=dev)
+        self.kind = torch.empty(max(pages, 1), dtype=torch.uint8, device=dev)
+        self.level = torch.empty(max(pages, 1), dtype=torch.uint8, device=dev)
+        self.meta, self.stats = self._ctx.bt_load(img, self.image, self.kind, self.level)
+        self.image_bytes = self.meta.num_pages * BT_PAGE_BYTES
+        return self.stats
+
+    def check(self) -> dict:
+        self.stats = dev_bt_check(self.image, self.image_bytes, self.meta, self.kind, self.level)
+        return self.stats
+
+    def get_batch(self, keys):
+        """BTree.Get for a key batch (anything as_keys takes): (status u8, out_off u64 n + 1, out_vals u8): key i's
+        value is out_vals[out_off[i]: out_off[i + 1]] where status[i] == GET_FOUND; GET_ERROR is an empty key or a
+        walk that met a page or a cell the image does not hold whole."""
+        import torch
+        kb = as_keys(keys)
+        n = kb.n
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint8)
+        dev = self.image.device
+        data = torch.from_numpy(kb.data.reshape(-1).copy() if kb.data.size else np.zeros(1, np.uint8)).to(dev)
+        if kb.offsets is not None:
+            dk = dev_keys(data, torch.from_numpy(kb.offsets.view(np.int64).copy()).to(dev))
+        else:
+            dk = dev_keys(data, n=n, stride=kb.stride)
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+        source = torch.empty(n, dtype=torch.uint8, device=dev)
+        vloc = torch.empty(n, dtype=torch.int64, device=dev)
+        vlen = torch.empty(n, dtype=torch.int32, device=dev)
+        dev_bt_get(self.image, self.image_bytes, self.meta, dk, status, None, None, vloc, vlen, source)
+        ws = torch.empty(dev_get_values_workspace_size(n), dtype=torch.uint8, device=dev)
+        sz = dev_get_values_plan(status, source, None, vloc, vlen, n, [], self.image, ws, pool_bytes=self.image_bytes)
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        out_vals = torch.empty(max(sz.val_bytes, 1), dtype=torch.uint8, device=dev)
+        dev_get_values_emit(status, source, None, vloc, vlen, n, [], self.image, sz, ws, out_off, out_vals if sz.val_bytes else None,
+                            pool_bytes=self.image_bytes)
+        torch.cuda.synchronize(dev)
+        return status.cpu().numpy(), out_off.cpu().numpy().view(np.uint64), out_vals.cpu().numpy()[: sz.val_bytes]
