@@ -41,7 +41,6 @@ constexpr uint64_t kBidMagic = 0x5344494B434F4C42ull;  // "BLOCKIDS"
 constexpr u64a kEmpty = ~0ull;
 enum : uint32_t { hMagic, hCells, hTable, hMaxUniq, hResident, hMisses, hBad, hUniq, hOverflow, hTiles };  // u64 words
 constexpr uint64_t kHeadBytes = 128;
-constexpr unsigned kStreamBlocks = 4096;  // most workgroups of a grid-stride launch
 
 struct BidIn {  // the cells and the residency table
     const uint16_t *cand;
@@ -267,11 +266,6 @@ inline BidWs ws_layout(void *ws, uint64_t cells, uint64_t max_uniq) {
     w.rank = w.minidx + w.table;
     w.sums = (uint64_t *)(p + kHeadBytes + 16 * w.table);
     return w;
-}
-
-inline unsigned stream_grid(uint64_t cells) {
-    const uint64_t b = (cells + 255) / 256;
-    return (unsigned)(b < kStreamBlocks ? b : kStreamBlocks);
 }
 
 hipError_t drained(hipStream_t s, hipError_t e) {

@@ -36,7 +36,6 @@ namespace seb {
 
 namespace {
 
-constexpr unsigned kStreamBlocks = 4096;  // most workgroups of a grid-stride launch
 enum : uint32_t { bLeaves = 0, bInternals, bBad, bReachLeaves, bReachInternals, bReachBad, bKeys, bDepth, bLeafLoInv, bLeafHi1, bWords };
 constexpr uint64_t kBtWsHead = 256;  // u64 counts[16], u32 changed[32]
 
@@ -181,11 +180,6 @@ __global__ __launch_bounds__(256) void k_bt_get(const uint8_t *__restrict__ imag
     }
 }
 
-inline unsigned grid_for(uint64_t items) {
-    const uint64_t b = (items + 255) / 256;
-    return (unsigned)(b < kStreamBlocks ? (b ? b : 1) : kStreamBlocks);
-}
-
 inline hipError_t drained(hipStream_t s, hipError_t e) {
     (void)hipStreamSynchronize(s);
     return e;
@@ -207,17 +201,17 @@ hipError_t launch_bt_check(const uint8_t *image, uint32_t np, uint32_t root, uin
     if ((e = hipMemsetAsync(ws, 0, kBtWsHead, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(lev, 0xFF, 4 * (uint64_t)np, s)) != hipSuccess) return e;
     if (bt_page_id_ok(root, np) && (e = hipMemsetAsync(lev + root, 0, 4, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bt_check, dim3(grid_for(64ull * np)), dim3(256), 0, s, image, np, kind);
+    hipLaunchKernelGGL(k_bt_check, dim3(stream_grid(64ull * np)), dim3(256), 0, s, image, np, kind);
     if ((e = hipGetLastError()) != hipSuccess) return drained(s, e);
     for (uint32_t r = 0; r + 1 < kBtMaxDepth && bt_page_id_ok(root, np); ++r) {
         uint32_t moved = 0;
-        hipLaunchKernelGGL(k_bt_level, dim3(grid_for(64ull * np)), dim3(256), 0, s, image, np, (const uint8_t *)kind, lev, r, changed + r);
+        hipLaunchKernelGGL(k_bt_level, dim3(stream_grid(64ull * np)), dim3(256), 0, s, image, np, (const uint8_t *)kind, lev, r, changed + r);
         if ((e = hipGetLastError()) != hipSuccess) return drained(s, e);
         if ((e = hipMemcpyAsync(&moved, changed + r, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return drained(s, e);
         if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
         if (!moved) break;
     }
-    hipLaunchKernelGGL(k_bt_stats, dim3(grid_for(np)), dim3(256), 0, s, image, np, (const uint8_t *)kind, (const uint32_t *)lev, level,
+    hipLaunchKernelGGL(k_bt_stats, dim3(stream_grid(np)), dim3(256), 0, s, image, np, (const uint8_t *)kind, (const uint32_t *)lev, level,
                        counts);
     if ((e = hipGetLastError()) != hipSuccess) return drained(s, e);
     uint64_t h[bWords];
@@ -232,7 +226,7 @@ hipError_t launch_bt_get(const uint8_t *image, uint32_t np, uint32_t root, const
                          uint32_t *pos, uint64_t *vloc, uint32_t *vlen, uint8_t *source, hipStream_t s) {
     if (kb.n == 0) return hipSuccess;
     const BtOut out{status, leaf, pos, vloc, vlen, source};
-    hipLaunchKernelGGL(k_bt_get<SEB_BT_LDS_ROOT != 0>, dim3(grid_for(kb.n)), dim3(256), 0, s, image, np, root, kb, out);
+    hipLaunchKernelGGL(k_bt_get<SEB_BT_LDS_ROOT != 0>, dim3(stream_grid(kb.n)), dim3(256), 0, s, image, np, root, kb, out);
     return hipGetLastError();
 }
 

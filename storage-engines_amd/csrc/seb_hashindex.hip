@@ -38,7 +38,6 @@ namespace {
 constexpr uint64_t kHeadBytes = kHidxHeadBytes;
 constexpr uint32_t kSegRecs = 256;
 constexpr uint32_t kSegLds = 36 * 1024;  // k_wal_crc's window
-constexpr unsigned kStreamBlocks = 4096;  // most workgroups of a grid-stride launch
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -250,11 +249,6 @@ __global__ __launch_bounds__(256) void k_hidx_get(const uint64_t *__restrict__ s
         if (out.vlen) out.vlen[i] = vl;
         if (out.source) out.source[i] = st == kGetFound ? 1 : 0;
     }
-}
-
-inline unsigned stream_grid(uint64_t n) {
-    const uint64_t b = (n + 255) / 256;
-    return (unsigned)(b < kStreamBlocks ? b : kStreamBlocks);
 }
 
 }  // namespace

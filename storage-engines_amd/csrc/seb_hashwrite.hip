@@ -45,7 +45,6 @@ typedef const __attribute__((address_space(1))) uint8_t *gbytes;
 constexpr uint32_t WT = kWriteTile;
 constexpr uint32_t SW = kScanWidth;
 constexpr uint64_t kCompactMagic = 0x5443504D43474553ull;  // "SEGCMPCT"
-constexpr unsigned kStreamBlocks = 4096;
 constexpr uint64_t kCutsEager = 1024;  // cuts copied back before their count is known
 
 // the frame's scratch (u64 words): the least bad op << 2 | reason, the image's size, the cuts' count, then the tiles' sums
@@ -447,11 +446,6 @@ __global__ __launch_bounds__(256) void k_off_shift(const uint64_t *__restrict__ 
 }
 
 inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
-
-inline unsigned stream_grid(uint64_t n) {
-    const uint64_t b = (n + 255) / 256;
-    return (unsigned)(b < kStreamBlocks ? b : kStreamBlocks);
-}
 
 hipError_t drained(hipStream_t s, hipError_t e) {
     (void)hipStreamSynchronize(s);

@@ -490,6 +490,18 @@ struct Options {
 };
 Options &options();
 
+// The grid of a 256-lane grid-stride launch over `items` >= 1: a workgroup per 256 items, at most `most` of them and
+// at most options().grid_cap (seb_blockids.hip, seb_hashindex.hip, seb_hashwrite.hip, seb_btree.hip and seb_values.hip's
+// copy).  The default grid_cap lies above both ceilings, so a default launch has min(ceil(items / 256), most)
+// workgroups; a test sets grid_cap to 1 or 2 and the kernels' loops take many trips on a small input.  Only for
+// kernels whose workgroups never wait for one another.
+constexpr unsigned kStreamBlocks = 4096;  // most workgroups of a grid-stride launch
+inline unsigned stream_grid(uint64_t items, unsigned most = kStreamBlocks) {
+    const uint64_t b = (items + 255) / 256;
+    const unsigned cap = most < options().grid_cap ? most : options().grid_cap;
+    return (unsigned)(b < cap ? (b ? b : 1) : cap);
+}
+
 hipError_t launch_build(const KeyBatch &kb, uint32_t *words, const ModArg &md, hipStream_t s);
 // Copy `bytes` of filter words to host-pinned memory (both 16-B aligned) with a kernel.
 hipError_t launch_copy_out(const uint32_t *words, uint8_t *host, uint64_t bytes, hipStream_t s);

@@ -363,8 +363,7 @@ hipError_t launch_values_emit(const ValuesArg &a, const void *sizes, void *ws, u
     hipLaunchKernelGGL(k_gv_offsets, dim3((unsigned)l.tiles), dim3(256), 0, s, a, hdr, sz, out_off, wsrc, wlen, wpad);
     if (sz.val_bytes) {
         const uint64_t groups = ((((uint64_t)out_vals & 15) + sz.val_bytes + 15) / 16 + 255) / 256;
-        const unsigned grid = (unsigned)(groups < kValCopyGrid ? groups : kValCopyGrid);
-        hipLaunchKernelGGL(k_gv_copy, dim3(grid), dim3(256), 0, s, hdr, sz, sz.n, out_off, wsrc, wlen, wpad, out_vals);
+        hipLaunchKernelGGL(k_gv_copy, dim3(stream_grid(256 * groups, kValCopyGrid)), dim3(256), 0, s, hdr, sz, sz.n, out_off, wsrc, wlen, wpad, out_vals);
     }
     return hipGetLastError();
 }

@@ -12,7 +12,12 @@ where the tree has depth <= 2 or was built fixed.
 get() answers what the library answers: the reference's walk with the bisection and the departures that
 include/seb_bloom.h states (a page type that is neither 1 nor 2, a touched cell that does not parse, a page id
 outside [1, num_pages) and a walk of more than MAX_DEPTH pages are ERROR).  On every internal page the check calls
-good it also runs findChild's linear scan and asserts that both agree."""
+good it also runs findChild's linear scan and asserts that both agree.
+
+Beside the trees that Put builds, cases() holds bulk-loaded images with pages wider than the 64 lanes a wave strides
+a directory with (leaves of 300 cells; internal pages of 63, 64, 65, 128, 129 and 133 cells) and chains of internal
+pages without a cell up to the depth limit; corrupt_cases() holds edits of the widest image behind cell 63, chains
+past the depth limit, and leaves at two levels.  corrupt_claims() states what each damaged image must give."""
 import struct
 
 import numpy as np
@@ -485,8 +490,8 @@ class Case:
     """image; puts: the Put dictionary where Get must equal it (depth <= 2 or a fixed build, no cell touched by
     hand), else None; keys: the keys that were Put (for probes); seps: every separator key of the image."""
 
-    def __init__(self, image, keys, puts=None):
-        self.image, self.keys, self.puts = image, sorted(keys), puts
+    def __init__(self, image, keys, puts=None, random3=0):
+        self.image, self.keys, self.puts, self.random3 = image, sorted(keys), puts, random3
         self.meta = open_image(image)
         self.seps = []
         for p in range(1, self.meta["num_pages"]):
@@ -509,6 +514,54 @@ def _deep(n, fixed):
     for i in order:
         t.put(_wide(int(i)), bytes([i % 251]) * 700)
     return t
+
+
+def _keys3(n, seed):
+    """n sorted distinct 3-byte keys."""
+    ids = np.sort(np.random.default_rng(seed).choice(1 << 24, n, replace=False))
+    return [int(i).to_bytes(3, "big") for i in ids]
+
+
+def _wide_case(n, leaf_cells, fanout, seed, random3=2000):
+    """Pages wider than a wave: n 3-byte keys with values b"" and b"v", bulk-loaded."""
+    keys = _keys3(n, seed)
+    vals = [b"v" if k[2] & 1 else b"" for k in keys]
+    return Case(bulk_load(keys, vals, leaf_cells=leaf_cells, fanout=fanout), keys, dict(zip(keys, vals)), random3)
+
+
+# (leaf_cells, fanout): internal pages of 63, 64, 65 and 128 cells, i.e. 64, 65, 66 and 129 children with the right
+# pointer: the widths at which the right pointer changes lane and pass of a 64-lane loop over i <= n
+BOUNDARY = ((63, 64), (64, 65), (65, 66), (128, 129))
+
+
+def widths(image):
+    """(the cell counts of the good leaves, of the good internal pages) of an image, as two sorted lists."""
+    n = open_image(image)["num_pages"]
+    out = {LEAF: [], INTERNAL: []}
+    for p in range(1, n):
+        pg = page_of(image, p)
+        if page_kind(pg, n) != BAD:
+            out[pg.type].append(pg.num_cells)
+    return sorted(out[LEAF]), sorted(out[INTERNAL])
+
+
+CHAIN_KEY, CHAIN_VALUE = b"end-of-chain", b"found"
+
+
+def chain_image(d):
+    """d internal pages without a cell, page i pointing right to page i + 1, then a one-key leaf: a tree of depth
+    d + 1 whose root is page 1.  MAX_DEPTH - 1 internal pages is the deepest tree that Get walks to its leaf."""
+    pages = []
+    for i in range(1, d + 1):
+        pg = Page(kind=INTERNAL)
+        pg.right_ptr = i + 1
+        pages.append(pg)
+    leaf = Page(kind=LEAF)
+    leaf.insert_cell(Cell(CHAIN_KEY, CHAIN_VALUE))
+    pages.append(leaf)
+    meta = bytearray(PAGE)
+    struct.pack_into(">IIII", meta, 0, MAGIC, 1, d + 2, 0)
+    return bytes(meta) + b"".join(bytes(p.d) for p in pages)
 
 
 _CACHE = {}
@@ -569,12 +622,21 @@ def cases():
         t.pages[pid] = new
     assert len(leaves) >= 4
     c["i_v1_mixed"] = Case(t.image(), list(t.puts), None)
+    # pages wider than a wave (a wave per page, the lanes striding the directory by 64)
+    c["j_wide_300"] = _wide_case(40_000, 300, 200, 300)      # leaves of 300 cells under a root of 133
+    c["k_wide_3level"] = _wide_case(40_000, 100, 130, 100)   # 400 leaves under internal pages of 129 cells
+    for lc, fo in BOUNDARY:
+        c["l_boundary_%d" % (fo - 1)] = _wide_case(2 * lc * fo, lc, fo, fo, random3=500)
+    # the deepest trees that Get still walks to the leaf: depth 31 and 32
+    for d in (30, 31):
+        c["m_chain_%d" % d] = Case(chain_image(d), [CHAIN_KEY], {CHAIN_KEY: CHAIN_VALUE})
     return c
 
 
-def probes(case, rng, cap=120):
+def probes(case, rng, cap=120, random3=None):
     """Present keys, absent keys between neighbours, keys below the minimum and above the maximum, every separator,
-    a present key with one byte appended and with its last byte dropped, the empty key."""
+    a present key with one byte appended and with its last byte dropped, the empty key; then random3 (default: the
+    case's) 3-byte keys, half of them present."""
     keys = case.keys
     pick = keys if len(keys) <= cap else [keys[i] for i in sorted(rng.choice(len(keys), cap, replace=False))]
     out = list(pick)
@@ -584,7 +646,18 @@ def probes(case, rng, cap=120):
     if keys:
         out += [keys[0][:-1], keys[0][:1], keys[-1] + b"\xff", keys[-1] + b"\0"]
     out += case.seps + [s + b"\0" for s in case.seps[:40]] + [s[:-1] for s in case.seps[:40]]
+    random3 = case.random3 if random3 is None else random3
+    if random3:
+        out += [keys[i] for i in rng.integers(0, len(keys), random3 // 2)]
+        out += [r.tobytes() for r in rng.integers(0, 256, (random3 - random3 // 2, 3), dtype=np.uint8)]
     return out
+
+
+def long_keys(case):
+    """Batch keys longer than any stored key, three of them a present key followed by zeros to around the 65,536
+    bytes that a compare looks at."""
+    k = case.keys[3]
+    return [k + b"\0" * 70000, b"\xff" * 66000, case.keys[0]] + [k + b"\0" * (n - len(k)) for n in (65535, 65536, 65537)]
 
 
 def _base_tree():
@@ -595,9 +668,22 @@ def _base_tree():
     return t
 
 
+_CORRUPT, _CLAIMS = {}, {}
+
+
+def corrupt_claims():
+    """name -> what a damaged image of corrupt_cases() must give beyond equality with the restatement: "bad": the
+    pages that the check calls bad (exactly these); "errors": whether more than the empty key's ERROR is answered;
+    "stats": counts of the check; "level": page -> level."""
+    corrupt_cases()
+    return _CLAIMS
+
+
 def corrupt_cases():
-    """name -> (image, probe keys): data errors that a status answers.  Every one but `unsorted` must give at least
-    one ERROR; `unsorted` is what the check must call bad."""
+    """name -> (image, probe keys): data errors that a status answers, built once per process.  corrupt_claims()
+    says which of them must give an ERROR and which pages the check must call bad."""
+    if _CORRUPT:
+        return _CORRUPT
     out = {}
     t = _base_tree()
     good = t.image()
@@ -606,7 +692,7 @@ def corrupt_cases():
     leaves = [t.pages[root].right_ptr] + [c.child for c in t.pages[root].cells()]
     n = len(t.pages)
 
-    def edit(fn, image=good):
+    def edit(fn, image=good):  # fn(bytes, the base tree's root page, page id -> page)
         b = bytearray(image)
         fn(b, Page(memoryview(b)[root * PAGE: (root + 1) * PAGE]), lambda p: Page(memoryview(b)[p * PAGE: (p + 1) * PAGE]))
         return bytes(b)
@@ -644,4 +730,66 @@ def corrupt_cases():
         a, c = p.cell_offset(1), p.cell_offset(2)
         p.set_cell_offset(1, c), p.set_cell_offset(2, a)
     out["unsorted"] = edit(unsorted)
-    return {k: (v, keys) for k, v in out.items()}
+    _CORRUPT.update({k: (v, keys) for k, v in out.items()})
+    _CLAIMS.update({k: dict(errors=k != "unsorted") for k in out})
+    _CLAIMS["unsorted"]["bad"] = [leaves[1]]
+
+    # ---- wide pages, each edit on the 300-cell image: exactly the edited page turns bad
+    wide = cases()["j_wide_300"]
+    wkeys = probes(wide, np.random.default_rng(23), random3=300)
+    wn, wroot = wide.meta["num_pages"], wide.meta["root"]
+    wleaf = page_of(wide.image, wroot).cell_at(70).child  # a leaf of 300 cells in the middle of the key space
+    assert page_of(wide.image, wleaf).num_cells == 300 and page_of(wide.image, wroot).num_cells > 128
+    # every key of the edited leaf and of the leaf under the root's edited cell: the bisections touch every cell
+    wkeys = wkeys + [c.key for p in (wleaf, page_of(wide.image, wroot).cell_at(100).child) for c in page_of(wide.image, p).cells()]
+
+    def swap(i, j):
+        def fn(b, rp, pg):
+            p = pg(wleaf)
+            a, c = p.cell_offset(i), p.cell_offset(j)
+            p.set_cell_offset(i, c), p.set_cell_offset(j, a)
+        return fn
+
+    def wide_case(name, fn, bad, errors):
+        _CORRUPT[name] = (edit(fn, wide.image), wkeys)
+        _CLAIMS[name] = dict(errors=errors, bad=[bad])
+
+    wide_case("wide_swap_63_64", swap(63, 64), wleaf, False)
+    wide_case("wide_swap_64_65", swap(64, 65), wleaf, False)
+    wide_case("wide_swap_last_pair", swap(298, 299), wleaf, False)
+    wide_case("wide_child_past_end_100", lambda b, rp, pg: struct.pack_into(">I", pg(wroot).d, child_field(pg(wroot), 100), wn + 5),
+              wroot, True)
+    wide_case("wide_cell_offset_4095_at_200", lambda b, rp, pg: pg(wleaf).set_cell_offset(200, 4095), wleaf, True)
+    wide_case("wide_duplicate_127_128", lambda b, rp, pg: pg(wleaf).set_cell_offset(128, pg(wleaf).cell_offset(127)), wleaf, False)
+
+    # ---- chains too deep for Get: the levels stop at MAX_DEPTH - 1, the leaf is never reached
+    for d in (32, 33):
+        _CORRUPT["chain_%d" % d] = (chain_image(d), [CHAIN_KEY, b"a", b"zzz", b""])
+        _CLAIMS["chain_%d" % d] = dict(errors=True, bad=[], stats=dict(depth=MAX_DEPTH, reach_leaves=0, reach_internals=MAX_DEPTH,
+                                                                        leaves=1, internals=d, keys=0, uniform=1))
+
+    # ---- leaves at two levels, a page with two parents (the depth-3 fixed build edited)
+    deep = cases()["f_depth3_fixed"]
+    dkeys = probes(deep, np.random.default_rng(29))
+    droot, dn = deep.meta["root"], deep.meta["num_pages"]
+    drp = page_of(deep.image, droot)
+    first, second = drp.right_ptr, drp.cell_at(0).child  # the root's two leftmost subtrees
+    leaf_a = page_of(deep.image, first).right_ptr
+    # the root points right at a level-2 leaf of its own first subtree: that subtree's page and other leaves are lost
+    _CORRUPT["two_levels"] = (edit(lambda b, rp, pg: setattr(pg(droot), "right_ptr", leaf_a), deep.image), dkeys)
+    _CLAIMS["two_levels"] = dict(errors=False, bad=[], level={leaf_a: 1}, stats=dict(uniform=0, reach_leaves=119, keys=345, leaves=138,
+                                                                                      internals=11, reach_internals=10, depth=3))
+    # the root's first cell points at that leaf, whose parent stays reachable: level 1 from the root, 2 from the parent
+    _CORRUPT["two_parents"] = (edit(lambda b, rp, pg: struct.pack_into(">I", pg(droot).d, child_field(pg(droot), 0), leaf_a), deep.image),
+                               dkeys)
+    lost = page_of(deep.image, second).num_cells + 1
+    _CLAIMS["two_parents"] = dict(errors=False, bad=[], level={leaf_a: 1, first: 1}, stats=dict(uniform=0, reach_leaves=138 - lost,
+                                                                                                 reach_internals=10, depth=3))
+    # the one leaf at another level is the image's last page: a copy of leaf_a appended, the root pointing right at it
+    b = bytearray(deep.image) + deep.image[leaf_a * PAGE: (leaf_a + 1) * PAGE]
+    struct.pack_into(">I", b, 8, dn + 1)
+    page_of(b, droot).right_ptr = dn
+    _CORRUPT["last_page_other_level"] = (bytes(b), dkeys)
+    _CLAIMS["last_page_other_level"] = dict(errors=False, bad=[], level={dn: 1}, stats=dict(uniform=0, leaves=139, depth=3,
+                                            reach_leaves=139 - (page_of(deep.image, first).num_cells + 1)))
+    return _CORRUPT

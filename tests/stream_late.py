@@ -11,6 +11,7 @@ Outputs (`Out`) start as 0xA5 between 64 guard bytes on either side; reading one
 
 `Rig` (one per module) measures the delay and runs the positive control: a stream is accepted only if a default-
 stream read made while S sits in its delay sees the poison, i.e. the null stream really runs ahead of S."""
+import contextlib
 import time
 
 import numpy as np
@@ -195,6 +196,15 @@ class Late:
         self.S.synchronize()
         assert self.done.query() is True
         self.keep = []
+
+
+CAPS = (None, 1, 2)  # the default grid, then at most one and two workgroups per grid-stride launch
+
+
+def grid_cap(seb, cap):
+    """A context in which the library's grid-stride launches have at most `cap` workgroups (None: as they are), so
+    that a small input takes the kernels' loops through several trips."""
+    return seb.option("grid_cap", cap) if cap else contextlib.nullcontext()
 
 
 def differ(want_good, want_poison, names=None):

@@ -75,16 +75,47 @@ def test_the_cases_hold_what_they_claim(seb):
     assert any(pg.is_leaf and pg.num_cells == 0 and pg.right_ptr != 0 for pg in pages)
     img, meta = CASES["i_v1_mixed"].image, CASES["i_v1_mixed"].meta
     assert {bref.page_of(img, p).d[9] for p in range(1, meta["num_pages"])} == {0, 1, 2}
+    # pages wider than a wave: leaves of 300 cells under a root of more than 128; several internal pages of 129
+    leaf_w, int_w = bref.widths(CASES["j_wide_300"].image)
+    assert leaf_w[-1] == 300 and leaf_w.count(300) > 100 and int_w == [133]
+    leaf_w, int_w = bref.widths(CASES["k_wide_3level"].image)
+    assert leaf_w[-1] == 100 and int_w.count(129) >= 3 and len(int_w) >= 5
+    assert seb.bt_check(CASES["k_wide_3level"].image, seb.bt_open(CASES["k_wide_3level"].image))[2]["depth"] == 3
+    # the boundary family: internal pages of exactly 63, 64, 65 and 128 cells, leaves one narrower
+    for lc, fo in bref.BOUNDARY:
+        leaf_w, int_w = bref.widths(CASES["l_boundary_%d" % (fo - 1)].image)
+        assert int_w == [1, fo - 1, fo - 1] and set(leaf_w) == {lc} and fo - 1 in (63, 64, 65, 128)
+    # the chains: depth 31 and 32, the key found behind 30 and 31 internal pages without a cell
+    for d in (30, 31):
+        case = CASES["m_chain_%d" % d]
+        st = seb.bt_check(case.image, seb.bt_open(case.image))[2]
+        assert st["depth"] == d + 1 and st["reach_internals"] == d and bref.widths(case.image) == ([1], [0] * d)
+    # every wide edit sits on a page of 300 cells (the root: more than 128)
+    for name, claim in bref.corrupt_claims().items():
+        if name.startswith("wide_"):
+            assert bref.page_of(CASES["j_wide_300"].image, claim["bad"][0]).num_cells in (300, 133), name
 
 
 @pytest.mark.parametrize("name", sorted(CORRUPT))
 def test_corrupt_image_is_answered_by_a_status(seb, name):
     image, keys = CORRUPT[name]
     got, stats, kind = against_ref(seb, image, keys, name)
+    claim = bref.corrupt_claims()[name]
     if name == "unsorted":
         assert stats["bad"] == 1 and stats["reach_bad"] == 1
-    else:
+    if claim["errors"]:
         assert (got[0] == bref.ERROR).sum() > 1, name  # more than the empty key's
+    else:
+        assert (got[0] == bref.ERROR).sum() == 1 and (got[0] == bref.FOUND).any() and (got[0] == bref.MISS).any(), name
+    if "bad" in claim:  # exactly these pages are bad
+        assert list(np.nonzero(kind == bref.BAD)[0]) == [0] + sorted(claim["bad"]), name
+    for k, v in claim.get("stats", {}).items():
+        assert stats[k] == v, (name, k, stats)
+    level = seb.bt_check(image, seb.bt_open(image))[1]
+    for p, lv in claim.get("level", {}).items():
+        assert level[p] == lv, (name, p)
+    if name.startswith("chain_"):  # every key, the present one too, ends at the 32nd page of the walk
+        assert (got[0] == bref.ERROR).all() and (got[1][:-1] == bref.MAX_DEPTH).all(), name
     if name == "self_pointer":  # the cycle ends at the 32nd page
         i = keys.index(b"a")
         assert got[0][i] == bref.ERROR and got[1][i] == bref.open_image(image)["root"]
@@ -97,7 +128,7 @@ def test_long_and_fixed_width_keys(seb):
     """A batch key longer than any stored key, and the fixed-stride layout."""
     case = CASES["e_root_split"]
     meta = seb.bt_open(case.image)
-    long = [case.keys[3] + b"\0" * 70000, b"\xff" * 66000, case.keys[0]]
+    long = bref.long_keys(case)
     got = seb.bt_get(case.image, meta, long)
     want = bref.get_batch(case.image, case.meta, long)
     for g, w in zip(got, want):

@@ -6,6 +6,8 @@ Sizes: 0, 1, 63, 64, 65, 255, 257, 2049 (two tiles of 1024 and one cell) and 300
 grid-stride kernels, 293 tiles, a ragged last one).  Patterns: blockids_ref.PATTERNS.  max_uniq is the exact count of
 distinct miss pairs, so the table runs at the fullest load it can have (for a power of two of pairs exactly one
 half), and `cells`, which gives another table size and so other probe chains: no output may depend on either.
+With the option grid_cap at 1 and 2, 1,300 cells take the loops of k_bid_resident, k_bid_insert and k_bid_emit through
+three trips, the last one partial; the outputs equal the default grid's byte for byte.
 
 The busy-stream case goes through tests/stream_late.py, the end-to-end case through the device builder and the
 restated LSM.Get of getpath_ref."""
@@ -142,6 +144,61 @@ def test_mixed_residency_table(seb, torch_cuda, cells):
     seb.dev_block_ids_resident(*d.args(), bid.t, None)
     torch.cuda.synchronize()
     sl.same(bid.get("bid"), resident_want(seb, d), "bid without counts")
+
+
+def capped_cells(torch, seb, name):
+    """1,300 cells: at most 2 workgroups take them in three trips, the last one partial."""
+    cand, blocks = bref.pattern(name, 1300)
+    table = bref.table_mixed() if name == "mixed" else (None, None)
+    d = Cells(torch, seb, cand, blocks, *table, id_base=11)
+    assert 2 * 256 * 2 < d.cells < 2 * 256 * 3
+    flat = d.bid.reshape(-1)
+    assert (flat[1024:] != NO_ID).any() and (flat[:1024] != NO_ID).any()
+    return d
+
+
+@pytest.mark.parametrize("name", ["mixed"])
+def test_resident_map_under_a_grid_cap(seb, torch_cuda, name):
+    """seb_dev_block_ids_resident (k_bid_resident) at 1 and 2 workgroups: ids and counts equal the host half's and
+    the default grid's."""
+    torch = torch_cuda
+    d = capped_cells(torch, seb, name)
+    want = resident_want(seb, d)
+    assert (want[1024:] != NO_ID).any()
+    runs = []
+    for cap in sl.CAPS:
+        bid, counts = sl.Out(torch, d.cells, np.uint32), sl.Out(torch, 3, np.uint64)
+        with sl.grid_cap(seb, cap):
+            seb.dev_block_ids_resident(*d.args(), bid.t, counts.t)
+            torch.cuda.synchronize()
+        sl.same(bid.get("bid"), want, f"{name} cap {cap}: resident bid")
+        assert tuple(int(x) for x in counts.get("counts")) == (d.sizes[1], d.sizes[2], d.sizes[4]), (name, cap)
+        runs.append((bid.get().tobytes(), counts.get().tobytes()))
+    assert runs[1] == runs[0] and runs[2] == runs[0]
+
+
+@pytest.mark.parametrize("name", ["mixed", "distinct", "7x3"])
+def test_plan_and_emit_under_a_grid_cap(seb, torch_cuda, name):
+    """The insert (k_bid_insert, inside the plan) and the emit (k_bid_emit) at 1 and 2 workgroups; the plan's tile
+    kernels keep their one workgroup per tile.  Sizes, ids and the unique blocks equal the host half's and the
+    default grid's."""
+    torch = torch_cuda
+    d = capped_cells(torch, seb, name)
+    uniq = d.sizes[3]
+    assert uniq > (1024 if name == "distinct" else 2) and d.sizes[2] > 512
+    runs = []
+    for cap in sl.CAPS:
+        ws = workspace(torch, seb, d.cells, uniq)
+        bid, us, ub = sl.Out(torch, d.cells, np.uint32), sl.Out(torch, uniq, np.uint16), sl.Out(torch, uniq, np.uint64)
+        with sl.grid_cap(seb, cap):
+            sz = seb.dev_block_ids_plan(*d.args(), uniq, ws)
+            assert sz.as_tuple() == d.sizes, (name, cap)
+            seb.dev_block_ids_emit(*d.args(), uniq, d.id_base, sz, ws, bid.t, us.t, ub.t)
+            torch.cuda.synchronize()
+        got = (bid.get("bid"), us.get("uniq_slot"), ub.get("uniq_block"))
+        bref.assert_same(got, (d.bid.reshape(-1), d.us, d.ub), f"{name} cap {cap}")
+        runs.append([g.tobytes() for g in got])
+    assert runs[1] == runs[0] and runs[2] == runs[0]
 
 
 def test_range_and_the_retry(seb, torch_cuda):

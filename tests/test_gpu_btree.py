@@ -5,7 +5,11 @@ restatement in test_btree.py and run under ASan + UBSan on the same bytes in tes
 the counts and (status, leaf, pos, vloc, vlen, source): on every shared case and every corrupt image, with the image
 at leads 0, 1 and 3 into its allocation, at batch sizes 0, 1, 63, 65 and 257, in the offsets layout and the fixed-
 stride one.  One bulk-loaded image of about 100,000 16-byte keys at depth 4 takes 300,000 probes, half of them
-absent.  Every output starts as 0xA5 between 64 guard bytes.  The entry points' refusals, one case on a busy side
+absent.  btree_ref's wide images (leaves of 300 cells, internal pages of 63, 64, 65, 128, 129 and 133) take a wave's
+lanes through several trips over a directory, its chains reach the depth limit from both sides, and three edited
+images hold leaves at two levels.  With the option grid_cap at 1 and 2 the grid-stride loops of all four kernels take
+several trips, the last one partial, and every output equals the default grid's byte for byte.  Batch keys of 65,535,
+65,536 and 65,537 bytes.  Every output starts as 0xA5 between 64 guard bytes.  The entry points' refusals, one case on a busy side
 stream with late inputs, and load -> get_batch -> values end to end against the reference, byte for byte.  The
 corrupt images are data errors that the kernels answer with a status through the bounds rules the header states;
 nothing here provokes a fault."""
@@ -99,8 +103,119 @@ def test_corrupt_images(seb, torch_cuda, name):
     """Data errors answered by a status, through the bounds rules that the sanitizer run exercised on these bytes."""
     image, keys = CORRUPT[name]
     want = check_and_get(torch_cuda, seb, image, keys, name, 1)
-    if name != "unsorted":
+    claim = bref.corrupt_claims()[name]
+    if claim["errors"]:
         assert (want[0] == bref.ERROR).sum() > 1, name
+    else:
+        assert (want[0] == bref.FOUND).any() and (want[0] == bref.MISS).any(), name
+    # what the image was made for, stated on the host half's answer that the device just equalled
+    meta = seb.bt_open(image)
+    w_kind, w_level, w_stats = seb.bt_check(image, meta)
+    if "bad" in claim:
+        assert list(np.nonzero(w_kind == bref.BAD)[0]) == [0] + sorted(claim["bad"]), name
+    assert all(w_stats[k] == v for k, v in claim.get("stats", {}).items()), (name, w_stats)
+    assert all(w_level[p] == lv for p, lv in claim.get("level", {}).items()), name
+
+
+def test_long_batch_keys(seb, torch_cuda):
+    """Batch keys of 65,535, 65,536 and 65,537 bytes and more: the compare looks at the first 65,536."""
+    torch, case = torch_cuda, CASES["e_root_split"]
+    meta = seb.bt_open(case.image)
+    nbytes = meta.num_pages * bref.PAGE
+    keys = bref.long_keys(case)
+    assert sorted(len(k) for k in keys)[1:4] == [65535, 65536, 65537]
+    want = seb.bt_get(case.image, meta, keys)
+    assert list(want[0]) == [bref.MISS] * 2 + [bref.FOUND] + [bref.MISS] * 3
+    d_image = lead_view(torch, case.image, 0)
+    for lead in (0, 3):
+        outs = dev_get(torch, seb, d_image, nbytes, meta, dev_keys_of(torch, seb, keys, lead), len(keys))
+        torch.cuda.synchronize()
+        same_get(outs, want, f"long keys, lead {lead}")
+
+
+# ------------------------------------------------------------------ capped grids: the grid-stride loops iterate
+
+def padded_probes(case, n, seed):
+    """n probe keys of a case: probes(), then present keys over again."""
+    keys = bref.probes(case, np.random.default_rng(seed))
+    return (keys + case.keys * (n // max(len(case.keys), 1) + 1))[:n]
+
+
+@pytest.mark.parametrize("name", ["f_depth3_fixed", "k_wide_3level", "two_parents"])
+def test_check_under_a_grid_cap(seb, torch_cuda, name):
+    """seb_dev_bt_check with at most 1 and 2 workgroups: a wave takes many pages in turn (k_bt_check, k_bt_level), on
+    the wide image its lanes many cells in turn as well, and k_bt_stats's lanes several pages.  Kind, level and every
+    count equal the host half's and the default grid's."""
+    torch = torch_cuda
+    image = CASES[name].image if name in CASES else CORRUPT[name][0]
+    meta = seb.bt_open(image)
+    np_ = meta.num_pages
+    # cap 2 = 8 waves: more than two trips of the page loop, the last one partial
+    assert np_ > 16 and np_ % 8 != 0 and np_ % 4 != 0, np_
+    if name == "k_wide_3level":  # k_bt_stats, a lane per page: a second, partial trip at cap 1
+        assert 256 < np_ < 512 and bref.widths(image)[1].count(129) >= 3
+    nbytes = np_ * bref.PAGE
+    d_image = lead_view(torch, image, 1)
+    w_kind, w_level, w_stats = seb.bt_check(image, meta)
+    runs = {}
+    for cap in sl.CAPS:
+        with sl.grid_cap(seb, cap):
+            kind, level, stats = dev_check(torch, seb, d_image, nbytes, meta)
+        runs[cap] = (kind.get("kind"), level.get("level"), stats)
+        sl.same(runs[cap][0], w_kind, f"{name} cap {cap}: kind")
+        sl.same(runs[cap][1], w_level, f"{name} cap {cap}: level")
+        assert stats == w_stats, (name, cap, stats, w_stats)
+    for cap in (1, 2):
+        assert runs[cap][0].tobytes() == runs[None][0].tobytes() and runs[cap][1].tobytes() == runs[None][1].tobytes()
+        assert runs[cap][2] == runs[None][2]
+
+
+def test_large_check_under_a_grid_cap(seb, torch_cuda, big):
+    """k_bt_stats's lane-per-page loop and its per-wave atomics over several trips: the large image's check."""
+    torch = torch_cuda
+    image = big[0]
+    meta = seb.bt_open(image)
+    np_ = meta.num_pages
+    assert np_ > 2 * 256 * 2 and np_ % 512 != 0 and np_ % 256 != 0, np_  # a lane per page: the last trip partial
+    nbytes = np_ * bref.PAGE
+    d_image = lead_view(torch, image, 0)
+    w_kind, w_level, w_stats = seb.bt_check(image, meta)
+    for cap in (1, 2):
+        with sl.grid_cap(seb, cap):
+            kind, level, stats = dev_check(torch, seb, d_image, nbytes, meta)
+        sl.same(kind.get("kind"), w_kind, f"cap {cap}: kind")
+        sl.same(level.get("level"), w_level, f"cap {cap}: level")
+        assert stats == w_stats, (cap, stats, w_stats)
+
+
+@pytest.mark.parametrize("layout", ["offsets", "stride16"])
+def test_get_under_a_grid_cap(seb, torch_cuda, big, layout):
+    """seb_dev_bt_get with at most 1 and 2 workgroups: a lane takes several keys in turn, the last trip partial."""
+    torch = torch_cuda
+    n = 1300
+    assert 2 * 256 * 2 < n < 2 * 256 * 3
+    if layout == "offsets":
+        case = CASES["k_wide_3level"]
+        image, keys = case.image, padded_probes(case, n, 31)
+        make = lambda: dev_keys_of(torch, seb, keys)  # noqa: E731
+    else:
+        image, keys = big[0], np.ascontiguousarray(big[2][:n])
+        make = lambda: seb.dev_keys(lead_view(torch, np.concatenate([keys.reshape(-1), np.zeros(1, np.uint8)]), 7), n=n, stride=16)  # noqa: E731
+    assert len(keys) == n
+    meta = seb.bt_open(image)
+    nbytes = meta.num_pages * bref.PAGE
+    d_image = lead_view(torch, image, 0)
+    want = seb.bt_get(image, meta, keys)
+    assert (want[0] == bref.FOUND).sum() > 100 and (want[0] == bref.MISS).sum() > 100
+    assert (want[0][1024:] == bref.FOUND).any()  # the third trip answers something that 0xA5 is not
+    runs = {}
+    for cap in sl.CAPS:
+        with sl.grid_cap(seb, cap):
+            outs = dev_get(torch, seb, d_image, nbytes, meta, make(), n)
+            torch.cuda.synchronize()
+        same_get(outs, want, f"{layout} cap {cap}")
+        runs[cap] = [o.get().tobytes() for o in outs]
+    assert runs[1] == runs[None] and runs[2] == runs[None]
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 65, 257])

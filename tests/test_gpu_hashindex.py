@@ -7,7 +7,9 @@ four times that), and again with the test-only option hidx_hash_mask = 3, under 
 four home slots, so the key compare and long probe chains decide every answer; the results must be identical.  One
 store of about 300,000 records over 100,000 keys in four segments.  A table of 4 slots for 1,000 keys is
 SEB_ERR_RANGE and the retry succeeds; two inserts equal one; bits flipped in the pool after the build turn exactly
-the flipped records' keys ERROR under verify and none without it.  Every output starts as 0xA5 between 64 guard
+the flipped records' keys ERROR under verify and none without it.  With the option grid_cap at 1 and 2, 1,354
+records and 1,300 keys take the loops of k_seg_live, k_hidx_insert and k_hidx_get through three trips, the last one
+partial, at hash masks 0 and 3; the outputs equal the default grid's byte for byte.  Every output starts as 0xA5 between 64 guard
 bytes.  The entry points' refusals, one case on a busy side stream with late inputs, and recover -> get_batch ->
 values end to end against the reference dict, byte for byte.  The corrupted inputs are data errors that the kernels
 answer with a status; nothing here provokes a fault."""
@@ -238,6 +240,87 @@ def test_two_inserts_equal_one(seb, torch_cuda, mask):
             torch.cuda.synchronize()
             same_get(seb, s, None, keys, True, outs, f"cut {cut}")
             table_guards(buf)
+
+
+# ------------------------------------------------------------------ capped grids: the grid-stride loops iterate
+
+def capped_store(torch, seb):
+    """thousand_keys() with a flipped bit in the first segment (live is 0 behind it), and a batch of 1,300 keys: at
+    most 2 workgroups take both in three trips, the last one partial."""
+    segments = thousand_keys()
+    off = seb.seg_scan(segments[0])[0]
+    segments[0] = href.flip(segments[0], int(off[400]) + 5, 2)
+    s = Store(torch, seb, segments)
+    rec = href.recover(segments)
+    keys = href.probes(rec, np.random.default_rng(21))
+    keys = (keys + sorted(rec["index"]))[:1300]
+    assert 2 * 256 * 2 < s.n < 2 * 256 * 3 and 2 * 256 * 2 < len(keys) < 2 * 256 * 3
+    assert 0 < int(s.live[:1024].sum()) < 1024 and s.live[1024:].any(), "every trip writes both values of live"
+    return s, rec, keys
+
+
+@pytest.mark.parametrize("mask", [0, 3])
+def test_verify_with_live_under_a_grid_cap(seb, torch_cuda, mask):
+    """seb_dev_seg_verify with live (k_seg_live) at 1 and 2 workgroups."""
+    torch = torch_cuda
+    s, _, _ = capped_store(torch, seb)
+    runs = {}
+    with seb.option("hidx_hash_mask", mask):
+        for cap in sl.CAPS:
+            with sl.grid_cap(seb, cap):
+                ok, valid, live = dev_verify(torch, seb, s)
+                torch.cuda.synchronize()
+            runs[cap] = [o.get(name) for o, name in ((ok, "ok"), (valid, "valid"), (live, "live"))]
+            for got, want, name in zip(runs[cap], (s.ok, s.valid, s.live), ("ok", "valid", "live")):
+                sl.same(got, want, f"cap {cap}: {name}")
+    assert all(a.tobytes() == b.tobytes() for cap in (1, 2) for a, b in zip(runs[cap], runs[None]))
+
+
+@pytest.mark.parametrize("mask", [0, 3])
+def test_insert_and_count_under_a_grid_cap(seb, torch_cuda, mask):
+    """seb_dev_hidx_insert / _count at 1 and 2 workgroups: the key count, and the table's answers to a default-grid
+    Get, equal the host half's and the default grid's.  (Which slot a key takes depends on the order of arrival, so
+    tables are compared through what they answer.)"""
+    torch = torch_cuda
+    s, rec, keys = capped_store(torch, seb)
+    capacity = len(rec["index"])
+    d_live = sl.to_dev(torch, s.live)
+    runs = {}
+    with seb.option("hidx_hash_mask", mask):
+        for cap in sl.CAPS:
+            buf, table = new_table(torch, seb, capacity)
+            with sl.grid_cap(seb, cap):
+                seb.dev_hidx_insert(table, capacity, s.d_pool, s.pool_bytes, s.d_off, d_live, s.n)
+                assert seb.dev_hidx_count(table, capacity) == (capacity, 0), cap
+            outs = dev_get(torch, seb, s, table, capacity, keys, True)
+            torch.cuda.synchronize()
+            st, distinct = same_get(seb, s, s.live, keys, True, outs, f"cap {cap}")
+            assert distinct == capacity and (st == href.FOUND).sum() > 500 and (st == href.MISS).any()
+            runs[cap] = [o.get().tobytes() for o in outs]
+            table_guards(buf)
+    assert runs[1] == runs[None] and runs[2] == runs[None]
+
+
+@pytest.mark.parametrize("verify", [True, False])
+@pytest.mark.parametrize("mask", [0, 3])
+def test_get_under_a_grid_cap(seb, torch_cuda, mask, verify):
+    """seb_dev_hidx_get at 1 and 2 workgroups, with the CRC check and without it."""
+    torch = torch_cuda
+    s, rec, keys = capped_store(torch, seb)
+    capacity = len(rec["index"])
+    runs = {}
+    with seb.option("hidx_hash_mask", mask):
+        buf, table = new_table(torch, seb, capacity)
+        seb.dev_hidx_insert(table, capacity, s.d_pool, s.pool_bytes, s.d_off, sl.to_dev(torch, s.live), s.n)
+        for cap in sl.CAPS:
+            with sl.grid_cap(seb, cap):
+                outs = dev_get(torch, seb, s, table, capacity, keys, verify)
+                torch.cuda.synchronize()
+            st, _ = same_get(seb, s, s.live, keys, verify, outs, f"cap {cap}")
+            assert (st[1024:] == href.FOUND).any() and (st[:1024] == href.FOUND).any()
+            runs[cap] = [o.get().tobytes() for o in outs]
+        table_guards(buf)
+    assert runs[1] == runs[None] and runs[2] == runs[None]
 
 
 # ------------------------------------------------------------------ verify

@@ -8,7 +8,8 @@ straddle 16-byte output boundaries), a store where every key ends deleted (an em
 (two CRC workgroups), and one 1 MiB value among 20-byte ones (the copy is split by output bytes).  Every output and
 the workspace start as 0xA5 between 64 guard bytes, images sit at odd byte alignments.  seb_hidx_compact against the
 host's compaction and read side.  HashIndex end to end: put_batch -> get_batch, then compact of the oldest 2 of 4
-segments of a 300,000-record store.  One case on a busy side stream with late inputs.  The refused inputs are data
+segments of a 300,000-record store.  With the option grid_cap at 1 and 2 the loops of k_sc_place, k_sc_copy,
+k_hidx_logical and k_off_shift take several trips, and the outputs equal the default grid's byte for byte.  One case on a busy side stream with late inputs.  The refused inputs are data
 errors answered with a status; nothing here provokes a fault."""
 import numpy as np
 import pytest
@@ -146,8 +147,9 @@ def test_frame_cut_capacity_and_refusals(seb, torch_cuda):
 
 # ------------------------------------------------------------------ compaction
 
-def dev_compact(torch, seb, pool, rec_off, live, what, pool_lead=1, image_lead=5):
-    """plan + emit on the device into guarded outputs against seb_seg_compact; returns the host's triple."""
+def dev_compact(torch, seb, pool, rec_off, live, what, pool_lead=1, image_lead=5, keep=None):
+    """plan + emit on the device into guarded outputs against seb_seg_compact; returns the host's triple.  keep: a
+    list that receives the device's (out_rec_off, image) bytes."""
     want_image, want_off, want = seb.seg_compact(pool, rec_off, live, TS)
     n = rec_off.size
     d_pool = lead_view(torch, pool, pool_lead)
@@ -164,6 +166,8 @@ def dev_compact(torch, seb, pool, rec_off, live, what, pool_lead=1, image_lead=5
     sl.same(out_off.get("out_rec_off"), want_off, f"{what}: out_rec_off")
     sl.same(image.get("image"), want_image, f"{what}: image")
     ws.get("workspace")
+    if keep is not None:
+        keep.append((out_off.get().tobytes(), image.get().tobytes()))
     return want_image, want_off, want
 
 
@@ -300,8 +304,11 @@ def test_logical_size(seb, torch_cuda, name):
 def test_hidx_compact_on_a_context(seb, torch_cuda, name, c):
     """The oldest c segments compacted through seb_hidx_compact: the new pool is the host's image followed by the
     segments that stay, the offsets and the table answer every Get as the store did before."""
-    torch = torch_cuda
-    segments = CASES[name]
+    hidx_compact_check(torch_cuda, seb, CASES[name], c)
+
+
+def hidx_compact_check(torch, seb, segments, c):
+    """Returns the bytes of the new pool, of the new offsets and of the Get's outputs."""
     s = upload_store(torch, seb, segments)
     want_image, want_off, want_sizes = seb.segs_compact(segments, c, TS)
     after = [want_image.tobytes()] + list(segments[c:])
@@ -339,6 +346,62 @@ def test_hidx_compact_on_a_context(seb, torch_cuda, name, c):
         sl.same(o.get(nm), w, nm)
     assert [int(x) for x in st] == [a[0] for a in wref.answers(segments, keys)]
     table.get("table")
+    return [dst.get().tobytes(), offs.tobytes()] + [o.get().tobytes() for o in outs]
+
+
+# ------------------------------------------------------------------ capped grids: the grid-stride loops iterate
+
+@pytest.mark.parametrize("mask", [0, 3])
+def test_compaction_under_a_grid_cap(seb, torch_cuda, mask):
+    """The compaction's plan (k_hidx_insert) and emit (k_sc_place, a lane per record; k_sc_copy, a lane per 16 output
+    bytes on four times the capped grid) at 1 and 2 workgroups: three trips over the records, two over the image's
+    chunks, the last ones partial.  Sizes, offsets and image equal the host's and the default grid's byte for byte."""
+    pool, rec_off, live = prefix_arrays(seb, many_keys(), 2)
+    assert 2 * 256 * 2 < rec_off.size < 2 * 256 * 3
+    keep = []
+    with seb.option("hidx_hash_mask", mask):
+        for cap in sl.CAPS:
+            with sl.grid_cap(seb, cap):
+                image, _, sizes = dev_compact(torch_cuda, seb, pool, rec_off, live, ("many keys", mask, cap), image_lead=3, keep=keep)
+    chunks = (3 + image.size + 15) // 16
+    assert 2 * 4 * 256 < chunks < 2 * 2 * 4 * 256 and sizes["survivors"] > 1024
+    assert keep[1] == keep[0] and keep[2] == keep[0]
+
+
+def test_logical_size_under_a_grid_cap(seb, torch_cuda):
+    """seb_dev_hidx_logical_size (k_hidx_logical, a lane per slot) at 1 and 2 workgroups: 16 and 8 trips over 4,096
+    slots, a wave's sum added once per wave."""
+    torch = torch_cuda
+    segments = many_keys()
+    s = upload_store(torch, seb, segments)
+    rec = href.recover(segments)
+    capacity = len(rec["index"])
+    assert seb.dev_hidx_table_bytes(capacity) == 64 + 8 * 4096
+    table = torch.zeros(seb.dev_hidx_table_bytes(capacity), dtype=torch.uint8, device="cuda")
+    seb.dev_hidx_insert(table, capacity, s["d_pool"], s["pool"].size, s["d_off"], s["d_live"], s["rec_off"].size)
+    want = seb.hidx_logical_size(s["pool"], s["rec_off"], s["live"])
+    assert want == wref.logical_size(segments, rec["index"]) > 10_000
+    for cap in sl.CAPS:
+        with sl.grid_cap(seb, cap):
+            assert seb.dev_hidx_logical_size(table, capacity, s["d_pool"], s["pool"].size) == want, cap
+
+
+def test_hidx_compact_under_a_grid_cap(seb, torch_cuda):
+    """seb_hidx_compact whole at 1 and 2 workgroups; the offset shift (k_off_shift) moves the 1,489 offsets of the
+    segments that stay, and the end offset, in three trips."""
+    w0 = href.Writer(100)
+    for i in range(100):
+        w0.put(b"old-%03d" % i, b"o" * (i % 9))
+    w0.put(b"key-00007", b"shadowed by the segments that stay")
+    segments = [w0.bytes()] + many_keys()
+    first = seb.segs_scan(segments)[2]
+    rest = int(first[3] - first[1])
+    assert 2 * 256 * 2 < rest + 1 < 2 * 256 * 3
+    runs = []
+    for cap in sl.CAPS:
+        with sl.grid_cap(seb, cap):
+            runs.append(hidx_compact_check(torch_cuda, seb, segments, 1))
+    assert runs[1] == runs[0] and runs[2] == runs[0]
 
 
 def test_hidx_compact_aborts_on_a_bad_record_and_reports_small_capacities(seb, torch_cuda):

@@ -6,7 +6,8 @@ of 1024 keys and one that needs two stretches of the tile-sum scan; value length
 chunks, 4083, one value of 70,000 bytes and one of 3 MiB among 1-byte values (the copy is balanced by output
 bytes); out_vals 16-byte aligned and at an odd address, sources at odd addresses, values at byte 0 and at the last
 byte of their source; the found patterns of test_gpu_getpath.patterns; pool only, one run only with a null run
-array, 8 runs and the pool, a run of no bytes behind a null pointer.  Outputs start as 0xA5 between 64 guard bytes.
+array, 8 runs and the pool, a run of no bytes behind a null pointer.  With the option grid_cap at 1 and 2 the copy's
+workgroups take 23 groups of 4 KiB in turns.  Outputs start as 0xA5 between 64 guard bytes.
 The plan names the lower of two invalid keys in different tiles.  A workspace that is another plan's makes the emit
 write nothing, and inputs rewritten between plan and emit leave every guard intact.  One case on a busy side stream
 with late inputs, and LSM.Get end to end: the values of every key of a batch over two memtable runs and four
@@ -123,6 +124,26 @@ def test_batch_sizes(seb, torch_cuda, n):
     for out_lead in (0, 1):
         sizes = check(torch_cuda, seb, b, f"n={n} out_lead={out_lead}", out_lead)
     assert sizes[1] > 0 or n == 1
+
+
+@pytest.mark.parametrize("out_lead", [0, 1])
+def test_copy_under_a_grid_cap(seb, torch_cuda, out_lead):
+    """The copy (k_gv_copy, a workgroup per 4 KiB of output) at 1 and 2 workgroups: each takes several groups in
+    turn, restaging its offsets every time; at 2 the last trip is one group.  Sizes, offsets and values equal the
+    host half's and the default grid's."""
+    torch = torch_cuda
+    rng = np.random.default_rng(2)
+    b = vref.make_batch(rng, 300, found=rng.random(300) < 0.7)  # 93,649 bytes: 23 groups
+    want = seb.get_values(*vref.batch_args(b))
+    groups = (out_lead + int(want[0][2]) + 4095) // 4096
+    assert groups > 2 * 2 and groups % 2 == 1, groups
+    runs = []
+    for cap in sl.CAPS:
+        with sl.grid_cap(seb, cap):
+            got = device_values(torch, seb, Dev(torch, b), out_lead=out_lead)
+        vref.assert_same(got, want, f"cap {cap} out_lead={out_lead}")
+        runs.append((got[0], got[1].tobytes(), got[2].tobytes()))
+    assert runs[1] == runs[0] and runs[2] == runs[0]
 
 
 def test_two_stretches_of_the_scan(seb, torch_cuda):
