@@ -231,9 +231,7 @@ hipError_t launch_route(const KeyBatch &kb, uint32_t bits, uint16_t *shard, uint
     if (kb.n == 0) return hipSuccess;
     if (bits > 16) return hipErrorInvalidValue;
     const uint32_t mask = bits ? ((1u << bits) - 1u) : 0u;
-    uint64_t g = (kb.n + 255) / 256;
-    if (g > 65536) g = 65536;
-    hipLaunchKernelGGL(k_route, dim3((unsigned)g), dim3(256), 0, s, kb, mask, shard, hash);
+    hipLaunchKernelGGL(k_route, dim3(stream_grid(kb.n, 65536)), dim3(256), 0, s, kb, mask, shard, hash);
     return hipGetLastError();
 }
 

@@ -491,10 +491,10 @@ struct Options {
 Options &options();
 
 // The grid of a 256-lane grid-stride launch over `items` >= 1: a workgroup per 256 items, at most `most` of them and
-// at most options().grid_cap (seb_blockids.hip, seb_hashindex.hip, seb_hashwrite.hip, seb_btree.hip and seb_values.hip's
-// copy).  The default grid_cap lies above both ceilings, so a default launch has min(ceil(items / 256), most)
-// workgroups; a test sets grid_cap to 1 or 2 and the kernels' loops take many trips on a small input.  Only for
-// kernels whose workgroups never wait for one another.
+// at most options().grid_cap (seb_blockids.hip, seb_hashindex.hip, seb_hashwrite.hip, seb_btree.hip, seb_values.hip's
+// copy and seb_codec.hip's k_route, whose ceiling is 65,536).  The default grid_cap lies above every ceiling, so a
+// default launch has min(ceil(items / 256), most) workgroups; a test sets grid_cap to 1 or 2 and the kernels' loops
+// take many trips on a small input.  Only for kernels whose workgroups never wait for one another.
 constexpr unsigned kStreamBlocks = 4096;  // most workgroups of a grid-stride launch
 inline unsigned stream_grid(uint64_t items, unsigned most = kStreamBlocks) {
     const uint64_t b = (items + 255) / 256;

@@ -33,6 +33,14 @@ def to_dev(torch, a):
     return torch.from_numpy(view.copy()).cuda()
 
 
+def lead_view(torch, a, lead):
+    """The bytes of `a` on the device, `lead` bytes into a 16-aligned allocation (16 readable bytes behind them)."""
+    a = np.asarray(a, np.uint8).reshape(-1)
+    buf = torch.from_numpy(np.concatenate([np.full(lead, 0xEE, np.uint8), a, np.zeros(16, np.uint8)])).cuda()
+    assert buf.data_ptr() % 16 == 0
+    return buf[lead: lead + a.size]
+
+
 class Rig:
     """The delay, the accepted stream and the figures the module docstring records."""
 

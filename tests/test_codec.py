@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import codec_c as cc
+import crc_ref as cr
 import keygen as kg
 
 FNV32A_KATS = [(b"", 0x811C9DC5), (b"a", 0xE40C292C), (b"ab", 0x4D2505CA), (b"abc", 0x1A47E90B),
@@ -79,6 +80,82 @@ def test_wal_oracle_flags_corruption():
     short[11] = short[10] + 20    # a 20-byte "record" cannot hold the header
     _, ok2 = cc.wal_crc(img, short[:12])
     assert ok2[10] == 0
+
+
+# ------------------------------------------------------------------ crc_ref: the edge cases the GPU tests share
+
+WAL_CASES = cr.wal_cases()
+SEG_CASES = cr.seg_cases()
+
+
+def test_crc_ref_coverage_by_hand():
+    """The restated geometry on inputs small enough to work out by hand."""
+    # 256 records of 144 bytes: 36,864 bytes; a lead of 1 makes the span 36,865 and a lead of 16 is no lead
+    off = np.arange(257, dtype=np.uint64) * 144
+    for lead, span, staged in ((0, 36864, True), (1, 36865, False), (15, 36879, False), (16, 36864, True)):
+        cov = cr.coverage(off, lead)
+        assert cov["span"] == [span] and cov["staged"] == [staged]
+        assert (cov["path"] == (cr.STAGED if staged else cr.DIRECT)).all()
+        assert cov["start4"][1] == (lead + 148) % 4 and cov["start16"][3] == (lead + 3 * 144 + 4) % 16 and (cov["len4"] == 0).all()
+    # records of 0..3 bytes are not checksummed; the second workgroup's base is its own first record's
+    off = np.concatenate([[0, 3, 3, 7], 7 + np.arange(1, 255) * 200]).astype(np.uint64)
+    cov = cr.coverage(off, 0)
+    assert cov["path"][:3].tolist() == [cr.REFUSED, cr.REFUSED, cr.DIRECT] and cov["len4"][2] == 0
+    assert cov["span"] == [7 + 253 * 200, 200 + 15] and cov["staged"] == [False, True]  # 50,607 = 15 mod 16
+    # the segment form: the span ends with the last record; a claim past the window is direct, past the pool refused
+    starts, ends = np.array([5, 100, 200]), np.array([60, 5000, 260])
+    cov = cr.coverage(starts, 3, ends, 6000)
+    assert cov["span"] == [3 + 260] and cov["path"].tolist() == [cr.STAGED, cr.DIRECT, cr.STAGED]
+    assert cr.coverage(starts, 3, ends, 4999)["path"].tolist() == [cr.STAGED, cr.REFUSED, cr.STAGED]
+    assert cr.coverage(starts, 3, np.array([60, 150, 6001]), 6000)["path"].tolist() == [cr.DIRECT, cr.DIRECT, cr.REFUSED]
+    assert cr.coverage(starts, 0, np.array([60, 150, 200 + cr.WINDOW]), 10**6)["staged"] == [False]
+    assert cr.coverage(starts, 0, np.array([60, 150, cr.WINDOW]), 10**6)["staged"] == [True]
+
+
+@pytest.mark.parametrize("name", sorted(WAL_CASES))
+def test_crc_ref_wal_cases(name):
+    """Each WAL case reaches its edge (by arithmetic), and its expectations are the oracle's."""
+    case = WAL_CASES[name]
+    for lead in (cr.LEADS if name.startswith(("sweep", "mixed")) else (None,)):
+        cr.assert_case(case, lead)
+    crc, ok = cc.wal_crc(case["image"], case["off"])
+    assert np.array_equal(crc, case["crc"]) and np.array_equal(ok, case["ok"])
+    lens = np.diff(case["off"].astype(np.int64))
+    assert not case["ok"][lens < 21].any()
+    if name.startswith("sweep"):
+        assert all((lens == n).any() for n in range(1, 75)) and case["ok"][(lens >= 21) & (lens < cr.LONG)].all()
+    if "kv" in case:
+        assert [21 + k + v for k, v in case["kv"]] == lens.tolist()
+
+
+@pytest.mark.parametrize("name", sorted(SEG_CASES))
+def test_crc_ref_seg_cases(seb, name):
+    """Each segment case reaches its edge, and its expectations are the host half's (seb_seg_verify)."""
+    case = SEG_CASES[name]
+    for lead in (cr.LEADS if name.startswith(("sweep", "mixed", "lying")) else (None,)):
+        cr.assert_case(case, lead)
+    first = case["first"]
+    n = len(case["off"])
+    assert first.tolist() == [b for b in (0, 100, 256, 333) if b < n] + [n] and n >= 256
+    ok, valid, _, live = seb.seg_verify(case["image"], case["off"], first, case["base"], case["size"])
+    assert np.array_equal(ok, case["ok"]) and np.array_equal(valid, case["valid"]) and np.array_equal(live, case["live"])
+    if "kv" in case:
+        assert [20 + k + v for k, v in case["kv"]] == (case["ends"] - case["off"].astype(np.int64)).tolist()
+        assert np.array_equal(seb.segs_scan([case["image"].tobytes()])[1], case["off"])
+
+
+@pytest.mark.parametrize("form", ["wal", "seg"])
+@pytest.mark.parametrize("with_long", [False, True])
+def test_crc_ref_frame_sweep_lengths(form, with_long):
+    """The batch that frames to the sweep's geometry: every pair and every alignment on the path it is meant for."""
+    lens = cr.frame_sweep_lengths(form, with_long)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    for lead in cr.LEADS + (7,):
+        cov = cr.coverage(off, lead) if form == "wal" else cr.coverage(off[:-1], lead, off[1:], int(off[-1]))
+        cr.assert_all_pairs(cov, cr.DIRECT if with_long else cr.STAGED)
+        cr.assert_all_starts(cov)
+        assert not any(cov["staged"]) if with_long else all(cov["staged"])
+        assert len(cov["staged"]) > 1
 
 
 def test_wal_scan_host_framing(seb):

@@ -16,12 +16,14 @@ answer with a status; nothing here provokes a fault."""
 import numpy as np
 import pytest
 
+import crc_ref as cr
 import hashindex_ref as href
 import stream_late as sl
 
 pytestmark = pytest.mark.gpu
 
 CASES = href.cases()
+SEG_CASES = cr.seg_cases()
 
 
 @pytest.fixture(scope="module")
@@ -31,11 +33,7 @@ def torch_cuda():
     return torch
 
 
-def lead_view(torch, a, lead):
-    """The bytes of `a` on the device, `lead` bytes into an aligned allocation."""
-    a = np.asarray(a, np.uint8).reshape(-1)
-    buf = torch.from_numpy(np.concatenate([np.full(lead, 0xEE, np.uint8), a, np.zeros(16, np.uint8)])).cuda()
-    return buf[lead: lead + a.size]
+lead_view = sl.lead_view  # the bytes of an array on the device, `lead` bytes into an aligned allocation
 
 
 class Store:
@@ -321,6 +319,77 @@ def test_get_under_a_grid_cap(seb, torch_cuda, mask, verify):
             runs[cap] = [o.get().tobytes() for o in outs]
         table_guards(buf)
     assert runs[1] == runs[None] and runs[2] == runs[None]
+
+
+# ------------------------------------------------------------------ crc_ref's cases: windows, alignments, lying sizes
+
+class CaseStore:
+    """A crc_ref segment case laid out like Store, its pool `lead` bytes off a 16-byte boundary."""
+
+    def __init__(self, torch, seb, case, lead):
+        self.pool, self.rec_off, self.first = case["image"], case["off"], case["first"]
+        self.ok, self.valid, _, self.live = seb.seg_verify(self.pool, self.rec_off, self.first, case["base"], case["size"])
+        self.n, self.nseg, self.pool_bytes = self.rec_off.size, self.first.size - 1, self.pool.size
+        self.d_pool = lead_view(torch, self.pool, lead)
+        assert self.d_pool.data_ptr() % 16 == lead % 16
+        self.d_off = sl.to_dev(torch, self.rec_off)
+        self.d_first = sl.to_dev(torch, self.first)
+
+
+def case_leads(case):
+    return cr.LEADS if not case["name"].startswith("window") else (case["lead"],)
+
+
+@pytest.mark.parametrize("name", sorted(SEG_CASES))
+def test_seg_verify_edge_cases(seb, torch_cuda, name):
+    """seb_dev_seg_verify on a crc_ref case (three or four segments, a boundary on a workgroup's edge and one inside
+    a workgroup): ok, valid and live equal the host half's and the restated rule's.
+
+    The lying_*_sealed cases are the ones that tell the two checksum paths apart: record 128 of a staged workgroup
+    claims bytes past the window, and its crc field matches exactly those bytes, so ok = 1 only if the checksum went
+    through crc_range over the pool (a walk of the window's LDS copy gives ok = 0).  In the unsealed ones a wrong path
+    and the right one both answer ok = 0.  Keep them."""
+    torch = torch_cuda
+    case = SEG_CASES[name]
+    for lead in case_leads(case):
+        cr.assert_case(case, lead)  # the input does what its name says, at this lead
+        s = CaseStore(torch, seb, case, lead)
+        inner = s.first[1:-1].tolist()
+        assert any(f % 256 for f in inner) and (256 in inner or s.n == 256)
+        ok, valid, live = dev_verify(torch, seb, s)
+        torch.cuda.synchronize()
+        for got, host, rule, what in ((ok, s.ok, case["ok"], "ok"), (valid, s.valid, case["valid"], "valid"),
+                                      (live, s.live, case["live"], "live")):
+            sl.same(got.get(what), host, f"{name} lead {lead}: {what}")
+            sl.same(host, rule, f"{name}: the host half's {what}")
+
+
+@pytest.mark.parametrize("name", sorted(n for n in SEG_CASES if n.startswith(("sweep", "lying"))))
+def test_get_with_verify_edge_cases(seb, torch_cuda, name):
+    """seb_dev_hidx_get with the CRC check over a crc_ref pool, every key its records state looked up and some absent
+    ones: over the live records, and over all records (then a record whose size field lies without a matching
+    checksum is found and answers ERROR; one that claims bytes past the pool never enters the table)."""
+    torch = torch_cuda
+    case = SEG_CASES[name]
+    keys = cr.seg_keys(case["image"], case["off"])
+    keys = keys + [b"absent-%d" % i for i in range(9)] + [k + b"\x00" for k in keys[:9]]
+    inside = case["ends"] <= case["image"].size
+    for lead in case_leads(case):
+        s = CaseStore(torch, seb, case, lead)
+        for live in (s.live, None):
+            st, _, _, _, distinct = seb.hidx_lookup(s.pool, s.rec_off, live, href.key_lists(keys), True)
+            assert (st == href.FOUND).sum() > 200 and (st == href.MISS).sum() >= 18
+            buf, table = new_table(torch, seb, len(keys))
+            seb.dev_hidx_insert(table, len(keys), s.d_pool, s.pool_bytes, s.d_off, None if live is None else sl.to_dev(torch, live), s.n)
+            skipped = int((~inside & (np.ones(s.n, bool) if live is None else live.astype(bool))).sum())
+            assert seb.dev_hidx_count(table, len(keys)) == (distinct, skipped), (name, lead)
+            for verify in (True, False):
+                outs = dev_get(torch, seb, s, table, len(keys), keys, verify)
+                torch.cuda.synchronize()
+                got, _ = same_get(seb, s, live, keys, verify, outs, f"{name} lead {lead} verify {verify}")
+                assert (got == href.ERROR).any() == (verify and live is None and name.startswith("lying") and
+                                                     "sealed" not in name and "past" not in name)
+            table_guards(buf)
 
 
 # ------------------------------------------------------------------ verify

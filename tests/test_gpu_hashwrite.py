@@ -14,6 +14,7 @@ errors answered with a status; nothing here provokes a fault."""
 import numpy as np
 import pytest
 
+import crc_ref as cr
 import hashindex_ref as href
 import hashwrite_ref as wref
 import stream_late as sl
@@ -40,11 +41,7 @@ def no_fallback(seb):
     assert seb.fallback_count() == before == 0
 
 
-def lead_view(torch, a, lead):
-    """The bytes of `a` on the device, `lead` bytes into an aligned allocation."""
-    a = np.asarray(a, np.uint8).reshape(-1)
-    buf = torch.from_numpy(np.concatenate([np.full(lead, 0xEE, np.uint8), a, np.zeros(16, np.uint8)])).cuda()
-    return buf[lead: lead + a.size]
+lead_view = sl.lead_view  # the bytes of an array on the device, `lead` bytes into an aligned allocation
 
 
 # ------------------------------------------------------------------ frame
@@ -67,6 +64,7 @@ def dev_frame(torch, seb, arrays, active, limit, what, image_lead=7):
     total, cuts = seb.dev_seg_frame_plan(dk, d_voff, d_del, rec_off.t, active, limit)
     assert total == want_image.size and cuts.tolist() == want_cuts.tolist(), what
     image = sl.Out(torch, total, np.uint8, lead=image_lead)
+    assert total == 0 or image.t.data_ptr() % 16 == image_lead % 16
     seb.dev_seg_frame_emit(dk, d_vals, d_voff, d_del, TS, rec_off.t, image.t, total)
     torch.cuda.synchronize()
     if n:
@@ -84,6 +82,40 @@ def test_frame_cases(seb, torch_cuda, name):
     for limit in (1, 100, 4096):
         for active in (0, limit - 1, limit, limit + 1):
             dev_frame(torch_cuda, seb, arrays, active, limit, (name, active, limit), image_lead=1 + (active & 7))
+
+
+def kv_ops(kv, seed):
+    """A Put batch with the given (key length, value length) per op."""
+    rng = np.random.default_rng(seed)
+    return [(bytes(rng.integers(0, 256, k, dtype=np.uint8)), bytes(rng.integers(0, 256, v, dtype=np.uint8))) for k, v in kv]
+
+
+@pytest.mark.parametrize("span,lead,shape", cr.WINDOW_PARAMS)
+def test_frame_seals_at_the_window_edges(seb, torch_cuda, span, lead, shape):
+    """The frame's seal (k_seg_crc in seal mode) where the first 256 records span exactly 36,863 / 36,864 / 36,865
+    bytes from the 16-aligned base below the image, a second workgroup behind them: the sealed image is the host
+    half's."""
+    ops = kv_ops(cr.kv_lengths("seg", cr.window_lengths(span, lead, shape, True)), seed=span + lead)
+    off = wref.frame(ops, TS)[1].astype(np.int64)
+    cov = cr.coverage(off[:-1], lead, off[1:], int(off[-1]))
+    cr.assert_window(dict(name=f"window_{span}"), cov)
+    assert len(cov["span"]) == 2
+    image, _ = dev_frame(torch_cuda, seb, wref.ops_arrays(ops), 0, seb.SEG_NO_LIMIT, (span, lead, shape), image_lead=lead)
+    assert image.tobytes() == wref.frame(ops, TS)[0]
+
+
+@pytest.mark.parametrize("with_long", [False, True])
+def test_frame_seals_every_alignment(seb, torch_cuda, with_long):
+    """Payloads of 1..70 bytes at every start alignment, all staged; and again with one 40,000-byte record in every
+    workgroup, so that the seal reads every short record straight from memory."""
+    ops = kv_ops(cr.kv_lengths("seg", cr.frame_sweep_lengths("seg", with_long)), seed=42)
+    off = wref.frame(ops, TS)[1].astype(np.int64)
+    for lead in (0, 7):
+        cov = cr.coverage(off[:-1], lead, off[1:], int(off[-1]))
+        cr.assert_all_pairs(cov, cr.DIRECT if with_long else cr.STAGED)
+        cr.assert_all_starts(cov)
+        assert not any(cov["staged"]) if with_long else all(cov["staged"])
+        dev_frame(torch_cuda, seb, wref.ops_arrays(ops), 0, seb.SEG_NO_LIMIT, ("sweep", with_long, lead), image_lead=lead)
 
 
 def test_frame_cut_capacity_and_refusals(seb, torch_cuda):

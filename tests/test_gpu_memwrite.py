@@ -15,6 +15,7 @@ entries), a stale index.  End to end: three batches -> frame -> replay -> three 
 import numpy as np
 import pytest
 
+import crc_ref as cr
 import memget_ref as gref
 import memtable_ref as mref
 import memwrite_ref as wref
@@ -105,7 +106,7 @@ def upload_ops(torch, seb, arrays, layout="varlen", with_deleted=True):
     return dk, hk, odd_view(torch, vals, 3), u64_dev(torch, voff), (odd_view(torch, dele, 5) if with_deleted else None)
 
 
-def device_frame(torch, seb, arrays, first_seq, layout="varlen", with_deleted=True, replay=True):
+def device_frame(torch, seb, arrays, first_seq, layout="varlen", with_deleted=True, replay=True, image_lead=7):
     keys, koff, vals, voff, dele = arrays
     n = len(voff) - 1
     dk, hk, dvals, dvoff, ddel = upload_ops(torch, seb, arrays, layout, with_deleted)
@@ -113,7 +114,8 @@ def device_frame(torch, seb, arrays, first_seq, layout="varlen", with_deleted=Tr
     rec = Guarded(torch, n + 1, np.uint64)
     total = seb.dev_wal_frame_plan(dk, dvoff, ddel, rec.view)
     assert total == want_img.size
-    img = Guarded(torch, total, lead=7)
+    img = Guarded(torch, total, lead=image_lead)
+    assert total == 0 or img.view.data_ptr() % 16 == image_lead % 16
     seb.dev_wal_frame_emit(dk, dvals, dvoff, ddel, first_seq, rec.view, img.view, image_bytes=total)
     got_off = rec.host(written=n > 0)
     if n:
@@ -171,6 +173,42 @@ def test_frame_edges(seb, torch_cuda):
     only_deletes = [(b"k%d" % i, b"carried", 1) for i in range(70)]
     device_frame(torch, seb, wref.op_arrays(only_deletes, 1, 1), first_seq=1)
     device_frame(torch, seb, wref.op_arrays([(b"", b"", 0)] * 70, 1, 1), first_seq=1)  # 21-byte records only
+
+
+def kv_ops(kv, seed):
+    """The arrays of a Put batch with the given (key length, value length) per op."""
+    rng = np.random.default_rng(seed)
+    koff = (5 + np.concatenate([[0], np.cumsum([k for k, _ in kv])])).astype(np.uint64)
+    voff = (9 + np.concatenate([[0], np.cumsum([v for _, v in kv])])).astype(np.uint64)
+    return (rng.integers(0, 256, int(koff[-1]), dtype=np.uint8), koff, rng.integers(0, 256, int(voff[-1]), dtype=np.uint8), voff,
+            np.zeros(len(kv), np.uint8))
+
+
+@pytest.mark.parametrize("span,lead,shape", cr.WINDOW_PARAMS)
+def test_frame_seals_at_the_window_edges(seb, torch_cuda, span, lead, shape):
+    """The frame's seal (k_wal_crc in seal mode) where the first 256 records span exactly 36,863 / 36,864 / 36,865
+    bytes from the 16-aligned base below the image, a second workgroup behind them: the sealed image is the host
+    half's, and every record passes SEB_WAL_VERIFY."""
+    arrays = kv_ops(cr.kv_lengths("wal", cr.window_lengths(span, lead, shape, True)), seed=span + lead)
+    want_off = seb.wal_frame_plan((arrays[0], arrays[1]), arrays[3], arrays[4])[0]
+    cov = cr.coverage(want_off, lead)
+    cr.assert_window(dict(name=f"window_{span}"), cov)
+    assert len(cov["span"]) == 2
+    device_frame(torch_cuda, seb, arrays, first_seq=5, replay=False, image_lead=lead)
+
+
+@pytest.mark.parametrize("with_long", [False, True])
+def test_frame_seals_every_alignment(seb, torch_cuda, with_long):
+    """Payloads of 1..70 bytes at every start alignment, all staged; and again with one 40,000-byte record in every
+    workgroup, so that the seal reads every short record straight from memory."""
+    arrays = kv_ops(cr.kv_lengths("wal", cr.frame_sweep_lengths("wal", with_long)), seed=41)
+    want_off = seb.wal_frame_plan((arrays[0], arrays[1]), arrays[3], arrays[4])[0]
+    for lead in (0, 7):
+        cov = cr.coverage(want_off, lead)
+        cr.assert_all_pairs(cov, cr.DIRECT if with_long else cr.STAGED)
+        cr.assert_all_starts(cov)
+        assert not any(cov["staged"]) if with_long else all(cov["staged"])
+        device_frame(torch_cuda, seb, arrays, first_seq=1 << 33, replay=False, image_lead=lead)
 
 
 def test_frame_refusals_name_the_host_halfs_op(seb, torch_cuda):
