@@ -6,6 +6,7 @@
 #include "seb_hashindex.h"
 #include "seb_hashwrite.h"
 #include "seb_host.h"
+#include "seb_stage.h"
 
 using namespace seb;
 
@@ -150,6 +151,54 @@ extern "C" int seb_dev_hidx_get(const void *table, uint64_t capacity, const uint
     return SEB_OK;
 }
 
+// The framing walk over `ns` segments of seg_bytes[s] bytes at pool offsets seg_base[s]: off = every record's pool offset,
+// first[s] = segment s's first record (ns + 1 entries); valid gets its ns entries.  images: each segment's own host bytes
+// (seb_hidx_recover); null: the segments lie back to back in `head` from seg_base[0] on (seb_hidx_compact).
+static int seg_walk(const uint8_t *const *images, const uint8_t *head, const uint64_t *seg_base, const uint64_t *seg_bytes,
+                    uint64_t ns, std::vector<uint64_t> &off, std::vector<uint64_t> &first, std::vector<uint64_t> &valid,
+                    uint8_t *short_tail, const char *who) {
+    try {
+        first.resize(ns + 1);
+        valid.resize(ns);
+        uint64_t n = 0;
+        for (uint64_t s = 0; s < ns; ++s) {
+            first[s] = n;
+            off.resize(n + seg_bytes[s] / seb::kSegHeader + 1);
+            uint64_t got = 0;
+            int tail = 0;
+            const uint8_t *image = images ? images[s] : head + (seg_base[s] - seg_base[0]);
+            if (seb::seg_scan(image, seg_bytes[s], seg_base[s], off.data() + n, off.size() - n, &got, &tail) != 0)
+                return fail(SEB_ERR_INTERNAL, "%s: segment %llu: the scan ran past its bound", who, (unsigned long long)s);
+            if (short_tail) short_tail[s] = (uint8_t)tail;
+            n += got;  // a short tail is no record
+        }
+        first[ns] = n;
+        off.resize(n);
+    } catch (const std::bad_alloc &) {
+        return hidx_rc(-3, who);
+    }
+    if (off.size() >= (1ull << 38)) return fail(SEB_ERR_INVALID, "%s: 2^38 records or more", who);
+    return SEB_OK;
+}
+
+// Both forms' first sections: the records' offsets, each segment's first record and valid count, a CRC and a live byte per record
+struct SegSections {
+    uint64_t off, first, valid, ok, live;
+    SegSections(Carver &c, uint64_t n, uint64_t ns)
+        : off(c.take(8 * n)), first(c.take(8 * (ns + 1))), valid(c.take(8 * ns)), ok(c.take(n)), live(c.take(n)) {}
+};
+
+// The walk's offsets up, the segments verified (w: the buffer the sections were carved from)
+static int seg_stage_verify(uint8_t *w, const SegSections &at, const std::vector<uint64_t> &off, const std::vector<uint64_t> &first,
+                            uint64_t ns, const uint8_t *pool, uint64_t pool_bytes, hipStream_t st) {
+    int rc;
+    if ((rc = upload(w + at.off, off.data(), 8 * off.size(), st)) || (rc = upload(w + at.first, first.data(), 8 * (ns + 1), st)))
+        return rc;
+    if (!ns) return SEB_OK;
+    return seb_dev_seg_verify(pool, pool_bytes, (const uint64_t *)(w + at.off), off.size(), (const uint64_t *)(w + at.first), ns,
+                              w + at.ok, (uint64_t *)(w + at.valid), w + at.live, st);
+}
+
 // Host images through the context: the framing walk on the host, the images and the offsets up, verify, clear and
 // insert on the compute stream, the per-segment counts and the table's state back.
 extern "C" int seb_hidx_recover(seb_ctx *c, const uint8_t *const *images, const uint64_t *image_bytes, uint64_t num_segments,
@@ -176,52 +225,29 @@ extern "C" int seb_hidx_recover(seb_ctx *c, const uint8_t *const *images, const 
     if (total && !dev_pool) return fail(SEB_ERR_INVALID, "%s: null pool", who);
     std::vector<uint64_t> off, first, base, dvalid;
     try {
-        first.resize(num_segments + 1);
         base.resize(num_segments + 1);
-        dvalid.resize(num_segments);
-        uint64_t at = 0, n = 0;
-        for (uint64_t s = 0; s < num_segments; ++s) {
-            first[s] = n, base[s] = at;
-            off.resize(n + image_bytes[s] / seb::kSegHeader + 1);
-            uint64_t got = 0;
-            int tail = 0;
-            if (seb::seg_scan(images[s], image_bytes[s], at, off.data() + n, off.size() - n, &got, &tail) != 0)
-                return fail(SEB_ERR_INTERNAL, "%s: segment %llu: the scan ran past its bound", who, (unsigned long long)s);
-            if (short_tail) short_tail[s] = (uint8_t)tail;
-            n += got, at += image_bytes[s];
-        }
-        first[num_segments] = n, base[num_segments] = at;
-        off.resize(n);
     } catch (const std::bad_alloc &) {
         return hidx_rc(-3, who);
     }
+    for (uint64_t s = 0; s < num_segments; ++s) base[s + 1] = base[s] + image_bytes[s];
+    if ((rc = seg_walk(images, nullptr, base.data(), image_bytes, num_segments, off, first, dvalid, short_tail, who))) return rc;
     const uint64_t n = off.size();
-    if (n >= (1ull << 38)) return fail(SEB_ERR_INVALID, "%s: 2^38 records or more", who);
     if (records) *records = n;
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OR_FAIL(hipSetDevice(c->device));
     hipStream_t st = c->s_comp;
-    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t a_first = up(8 * n), a_valid = a_first + up(8 * (num_segments + 1)), a_ok = a_valid + up(8 * num_segments),
-                   a_live = a_ok + up(n);
-    if ((rc = c->hx_ws.reserve(a_live + up(n) + 16))) return rc;
+    Drain drain{st};
+    Carver ws;
+    const SegSections at(ws, n, num_segments);
+    if ((rc = c->hx_ws.reserve(ws.bytes()))) return rc;
     uint8_t *w = (uint8_t *)c->hx_ws.p;
-    // the vectors die with this frame: whichever way it is left, what the stream holds is waited for first
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{st};
     for (uint64_t s = 0; s < num_segments; ++s)
         if (image_bytes[s]) HIP_OR_FAIL(hipMemcpyAsync(dev_pool + base[s], images[s], image_bytes[s], hipMemcpyHostToDevice, st));
-    if (n) HIP_OR_FAIL(hipMemcpyAsync(w, off.data(), 8 * n, hipMemcpyHostToDevice, st));
-    HIP_OR_FAIL(hipMemcpyAsync(w + a_first, first.data(), 8 * (num_segments + 1), hipMemcpyHostToDevice, st));
-    if (num_segments &&
-        (rc = seb_dev_seg_verify(dev_pool, total, (const uint64_t *)w, n, (const uint64_t *)(w + a_first), num_segments, w + a_ok,
-                                 (uint64_t *)(w + a_valid), w + a_live, st)))
-        return rc;
+    if ((rc = seg_stage_verify(w, at, off, first, num_segments, dev_pool, total, st))) return rc;
     if ((rc = seb_dev_hidx_clear(dev_table, capacity, st))) return rc;
-    if ((rc = seb_dev_hidx_insert(dev_table, capacity, dev_pool, total, (const uint64_t *)w, w + a_live, n, st))) return rc;
-    if (num_segments) HIP_OR_FAIL(hipMemcpyAsync(dvalid.data(), w + a_valid, 8 * num_segments, hipMemcpyDeviceToHost, st));
+    if ((rc = seb_dev_hidx_insert(dev_table, capacity, dev_pool, total, (const uint64_t *)(w + at.off), w + at.live, n, st)))
+        return rc;
+    if ((rc = download(dvalid.data(), w + at.valid, 8 * num_segments, st))) return rc;
     uint64_t keys = 0;
     const int count_rc = seb_dev_hidx_count(dev_table, capacity, &keys, nullptr, st);  // synchronises
     if (count_rc != SEB_OK && count_rc != SEB_ERR_RANGE) return count_rc;
@@ -500,60 +526,36 @@ extern "C" int seb_hidx_compact(seb_ctx *c, const uint8_t *dev_pool, uint64_t po
     if (rest_records && (!rest_rec_off || ((uintptr_t)rest_rec_off & 7)))
         return fail(SEB_ERR_INVALID, "%s: rest_rec_off is null or not 8-byte aligned", who);
     if (!new_rec_off || ((uintptr_t)new_rec_off & 7)) return fail(SEB_ERR_INVALID, "%s: new_rec_off is null or not 8-byte aligned", who);
+    std::vector<uint8_t> head;
+    std::vector<uint64_t> off, first, dvalid;
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OR_FAIL(hipSetDevice(c->device));
     hipStream_t st = c->s_comp;
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{st};
-    std::vector<uint8_t> head;
-    std::vector<uint64_t> off, first, dvalid;
+    Drain drain{st};
     try {
         head.resize(head_bytes);
-        if (head_bytes) {
-            HIP_OR_FAIL(hipMemcpyAsync(head.data(), dev_pool + head_at, head_bytes, hipMemcpyDeviceToHost, st));
-            HIP_OR_FAIL(hipStreamSynchronize(st));
-        }
-        first.resize(cs + 1);
-        dvalid.resize(cs);
-        uint64_t n = 0;
-        for (uint64_t s = 0; s < cs; ++s) {
-            first[s] = n;
-            off.resize(n + seg_bytes[s] / seb::kSegHeader + 1);
-            uint64_t got = 0;
-            int tail = 0;
-            if (seb::seg_scan(head.data() + (seg_base[s] - head_at), seg_bytes[s], seg_base[s], off.data() + n, off.size() - n, &got,
-                              &tail) != 0)
-                return fail(SEB_ERR_INTERNAL, "%s: segment %llu: the scan ran past its bound", who, (unsigned long long)s);
-            n += got;  // a short tail is no record: its bytes are not copied
-        }
-        first[cs] = n;
-        off.resize(n);
-        std::vector<uint8_t>().swap(head);
     } catch (const std::bad_alloc &) {
         return hidx_rc(-3, who);
     }
+    if ((rc = download(head.data(), dev_pool + head_at, head_bytes, st))) return rc;
+    if (head_bytes) HIP_OR_FAIL(hipStreamSynchronize(st));
+    if ((rc = seg_walk(nullptr, head.data(), seg_base, seg_bytes, cs, off, first, dvalid, nullptr, who))) return rc;
+    std::vector<uint8_t>().swap(head);
     const uint64_t n = off.size();
-    if (n >= (1ull << 38)) return fail(SEB_ERR_INVALID, "%s: 2^38 records or more", who);
-    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t a_first = up(8 * n), a_valid = a_first + up(8 * (cs + 1)), a_ok = a_valid + up(8 * cs), a_live = a_ok + up(n),
-                   a_plan = a_live + up(n), plan_bytes = n ? segcompact_ws_layout(n).bytes : 0;
-    if ((rc = c->hx_ws.reserve(a_plan + plan_bytes + 16))) return rc;
+    Carver ws;
+    const SegSections sec(ws, n, cs);
+    const uint64_t plan_bytes = n ? segcompact_ws_layout(n).bytes : 0, a_plan = ws.take(plan_bytes);
+    if ((rc = c->hx_ws.reserve(ws.bytes()))) return rc;
     uint8_t *w = (uint8_t *)c->hx_ws.p;
-    if (n) HIP_OR_FAIL(hipMemcpyAsync(w, off.data(), 8 * n, hipMemcpyHostToDevice, st));
-    HIP_OR_FAIL(hipMemcpyAsync(w + a_first, first.data(), 8 * (cs + 1), hipMemcpyHostToDevice, st));
-    if ((rc = seb_dev_seg_verify(dev_pool, pool_bytes, (const uint64_t *)w, n, (const uint64_t *)(w + a_first), cs, w + a_ok,
-                                 (uint64_t *)(w + a_valid), w + a_live, st)))
-        return rc;
-    HIP_OR_FAIL(hipMemcpyAsync(dvalid.data(), w + a_valid, 8 * cs, hipMemcpyDeviceToHost, st));
+    if ((rc = seg_stage_verify(w, sec, off, first, cs, dev_pool, pool_bytes, st))) return rc;
+    if ((rc = download(dvalid.data(), w + sec.valid, 8 * cs, st))) return rc;
     HIP_OR_FAIL(hipStreamSynchronize(st));
     for (uint64_t s = 0; s < cs; ++s)  // compactSegments returns the error: nothing is compacted
         if (dvalid[s] < first[s + 1] - first[s])
             return fail(SEB_ERR_INVALID, "%s: segment %llu: record %llu fails its CRC: the compaction is aborted", who,
                         (unsigned long long)s, (unsigned long long)dvalid[s]);
-    if ((rc = seb_dev_seg_compact_plan(dev_pool, pool_bytes, (const uint64_t *)w, nullptr, n, w + a_plan, plan_bytes, sizes, st)))
-        return rc;
+    const uint64_t *doff = (const uint64_t *)(w + sec.off);
+    if ((rc = seb_dev_seg_compact_plan(dev_pool, pool_bytes, doff, nullptr, n, w + a_plan, plan_bytes, sizes, st))) return rc;
     const uint64_t image = sizes->image_bytes, surv = sizes->survivors, total = image + rest_bytes;
     new_seg_base[0] = 0, new_seg_bytes[0] = image;
     for (uint64_t s = cs; s < num_segments; ++s)
@@ -563,7 +565,7 @@ extern "C" int seb_hidx_compact(seb_ctx *c, const uint8_t *dev_pool, uint64_t po
                     (unsigned long long)(surv + rest_records + 1));
     if (total >= seb::kHidxPoolLimit) return hidx_rc(-2, who);
     if (total && !dst_pool) return fail(SEB_ERR_INVALID, "%s: null destination pool", who);
-    if ((rc = seb_dev_seg_compact_emit(dev_pool, pool_bytes, (const uint64_t *)w, n, timestamp, sizes, w + a_plan, plan_bytes, dst_pool,
+    if ((rc = seb_dev_seg_compact_emit(dev_pool, pool_bytes, doff, n, timestamp, sizes, w + a_plan, plan_bytes, dst_pool,
                                        new_rec_off, st)))
         return rc;
     if (rest_bytes) HIP_OR_FAIL(hipMemcpyAsync(dst_pool + image, dev_pool + rest_at, rest_bytes, hipMemcpyDeviceToDevice, st));

@@ -3,6 +3,9 @@
 // build / probe dispatchers.
 //   seb_host.cpp      errors, options, workspace, dispatch, the seb_dev_* bloom entry points, shard + WAL
 //   seb_ctx.cpp       contexts, the chunk loops, seb_build / seb_probe / seb_probe_multi
+//   seb_stage.h       what the host-buffer forms on a context share (only .cpp files include it): up16, Drain, the section
+//                     carver over a DevBuf, the two copy helpers, an op batch, the runs and a sorted run's outputs on the
+//                     device (the longer functions: seb_stage.cpp); its first part compiles without HIP
 //   seb_filter.cpp    the Go-API filter handle and its CPU fallback
 //   seb_registry.cpp  the registry, MultiGet, the index walk and the block locator
 //   seb_sstable.cpp   the block-search, SSTable-builder and compaction-merge entry points
@@ -26,7 +29,7 @@
 //   seb_hashwrite.cpp the host half of the hash index's write side: frame and cuts, compaction, logical size (no HIP
 //                     dependency; seb_hashwrite.h)
 //   seb_hashwrite.hip its kernels (the seal: k_seg_crc's seal mode in seb_hashindex.hip; what both share: seb_hidx_dev.h)
-//   seb_hidx.cpp      the hash index's entry points, seb_hidx_recover and seb_hidx_compact
+//   seb_hidx.cpp      the hash index's entry points, seb_hidx_recover and seb_hidx_compact (their segment walk and sections)
 //   seb_btree.h      the B-tree's page codec, page rules and walk: one text for the host half and the kernels
 //   seb_btree.cpp    the host half of the B-tree's read side: open, check, Get (no HIP dependency)
 //   seb_btree.hip    its kernels: the page check, the level rounds, the counts, Get

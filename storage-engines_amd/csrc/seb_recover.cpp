@@ -8,6 +8,7 @@
 #include "seb_getpath.h"
 #include "seb_host.h"
 #include "seb_memtable.h"
+#include "seb_stage.h"
 #include "seb_values.h"
 
 using namespace seb;
@@ -150,20 +151,16 @@ extern "C" int seb_wal_recover(seb_ctx *c, const uint8_t *image, uint64_t bytes,
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OR_FAIL(hipSetDevice(c->device));
     hipStream_t s = c->s_comp;
-    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t img_bytes = off[n], a_off = up(img_bytes), a_ok = a_off + up(8 * (n + 1));
-    if ((rc = c->rpl_in.reserve(a_ok + up(n)))) return rc;
-    uint8_t *in = (uint8_t *)c->rpl_in.p;
-    const uint64_t *doff = (const uint64_t *)(in + a_off);
-    // off and ok die with this frame: whichever way it is left, what the stream holds is waited for first
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{s};
-    HIP_OR_FAIL(hipMemcpyAsync(in, image, img_bytes, hipMemcpyHostToDevice, s));
-    HIP_OR_FAIL(hipMemcpyAsync(in + a_off, off.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if ((rc = seb_dev_wal_crc(in, doff, n, SEB_WAL_VERIFY, nullptr, in + a_ok, s))) return rc;
-    HIP_OR_FAIL(hipMemcpyAsync(ok.data(), in + a_ok, n, hipMemcpyDeviceToHost, s));
+    Drain drain{s};
+    Carver inc;  // the image, its records' offsets, a byte per record
+    const uint64_t img_bytes = off[n], a_img = inc.take(img_bytes), a_off = inc.take(8 * (n + 1)), a_ok = inc.take(n);
+    if ((rc = c->rpl_in.reserve(inc.bytes()))) return rc;
+    uint8_t *in = section(c->rpl_in, a_img), *dok = section(c->rpl_in, a_ok);
+    const uint64_t *doff = nullptr;
+    if ((rc = upload(in, image, img_bytes, s)) || (rc = upload(&doff, section(c->rpl_in, a_off), off.data(), 8 * (n + 1), s)))
+        return rc;
+    if ((rc = seb_dev_wal_crc(in, doff, n, SEB_WAL_VERIFY, nullptr, dok, s))) return rc;
+    if ((rc = download(ok.data(), dok, n, s))) return rc;
     HIP_OR_FAIL(hipStreamSynchronize(s));
     // ReadAll's order: it meets a complete record that fails its CRC before it meets the truncated tail
     for (uint64_t i = 0; i < n; ++i)
@@ -173,26 +170,15 @@ extern "C" int seb_wal_recover(seb_ctx *c, const uint8_t *image, uint64_t bytes,
     const uint64_t ws_bytes = replay_ws_layout(n).bytes;
     if ((rc = c->rpl_ws.reserve(ws_bytes, true))) return rc;
     if ((rc = seb_dev_wal_replay_plan(in, doff, n, c->rpl_ws.p, ws_bytes, sizes, s))) return rc;
-    if (sizes->entries_out > entry_cap || sizes->key_bytes > key_cap || sizes->val_bytes > val_cap)
-        return fail(SEB_ERR_RANGE, "%s: a capacity is below its size (%llu entries, %llu key bytes, %llu value bytes); "
-                    "retry with *sizes", who, (unsigned long long)sizes->entries_out, (unsigned long long)sizes->key_bytes,
-                    (unsigned long long)sizes->val_bytes);
-    const uint64_t no = sizes->entries_out;
-    if ((no && !deleted) || (sizes->key_bytes && !keys) || (sizes->val_bytes && !vals))
-        return fail(SEB_ERR_INVALID, "%s: null output", who);
-    const uint64_t o_koff = up(sizes->key_bytes), o_vals = o_koff + up(8 * (no + 1)), o_voff = o_vals + up(sizes->val_bytes),
-                   o_del = o_voff + up(8 * (no + 1)), o_seq = o_del + up(no), out_bytes = o_seq + up(8 * no);
-    if ((rc = c->rpl_out.reserve(std::max<uint64_t>(out_bytes, 16)))) return rc;
+    const RunDst dst{keys, key_cap, key_off, vals, val_cap, val_off, deleted, seq, entry_cap};
+    if ((rc = check_run_dst(who, dst, sizes->entries_out, sizes->key_bytes, sizes->val_bytes))) return rc;
+    const RunOut at(sizes->key_bytes, sizes->val_bytes, sizes->entries_out);
+    if ((rc = c->rpl_out.reserve(at.bytes))) return rc;
     uint8_t *o = (uint8_t *)c->rpl_out.p;
-    if ((rc = seb_dev_wal_replay_emit(in, doff, sizes, c->rpl_ws.p, ws_bytes, o, (uint64_t *)(o + o_koff), o + o_vals,
-                                      (uint64_t *)(o + o_voff), o + o_del, seq ? (uint64_t *)(o + o_seq) : nullptr, s)))
+    if ((rc = seb_dev_wal_replay_emit(in, doff, sizes, c->rpl_ws.p, ws_bytes, o, (uint64_t *)(o + at.koff), o + at.vals,
+                                      (uint64_t *)(o + at.voff), o + at.del, seq ? (uint64_t *)(o + at.seq) : nullptr, s)))
         return rc;
-    if (sizes->key_bytes) HIP_OR_FAIL(hipMemcpyAsync(keys, o, sizes->key_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(key_off, o + o_koff, 8 * (no + 1), hipMemcpyDeviceToHost, s));
-    if (sizes->val_bytes) HIP_OR_FAIL(hipMemcpyAsync(vals, o + o_vals, sizes->val_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(val_off, o + o_voff, 8 * (no + 1), hipMemcpyDeviceToHost, s));
-    if (no) HIP_OR_FAIL(hipMemcpyAsync(deleted, o + o_del, no, hipMemcpyDeviceToHost, s));
-    if (no && seq) HIP_OR_FAIL(hipMemcpyAsync(seq, o + o_seq, 8 * no, hipMemcpyDeviceToHost, s));
+    if ((rc = run_download(o, at, dst, s))) return rc;
     HIP_OR_FAIL(hipStreamSynchronize(s));
     return SEB_OK;
 }
@@ -520,77 +506,33 @@ extern "C" int seb_memtable_get(seb_ctx *c, const seb_keys *kb, const seb_run *r
     if ((rc = check_keys(kb, who)) || (rc = validate_offsets(kb, who))) return rc;
     if (num_runs > SEB_MEM_MAX_RUNS || (num_runs && !runs) || (kb->n && !status)) return memget_rc(-1, -1, 0, who);
     if (kb->n >= (1ull << 32)) return memget_rc(-6, -1, 0, who);
-    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
-    uint64_t total = 16;
-    for (uint32_t r = 0; r < num_runs; ++r) {
-        const seb_run &u = runs[r];
-        if (u.n >= (1ull << 32)) return memget_rc(-5, (int)r, 0, who);
-        if (u.n && (!u.key_off || !u.val_off || (!u.keys && u.key_bytes))) return memget_rc(-1, -1, 0, who);
-        if (u.n) total += up(u.key_bytes) + 2 * up(8 * (u.n + 1)) + up(u.n) + up(8 * u.n) + up(run_index_bytes(u.n));
-    }
+    uint32_t bad_run = 0;
+    if ((rc = memget_rc(check_host_runs(runs, num_runs, SEB_MEM_MAX_RUNS, &bad_run), (int)bad_run, 0, who))) return rc;
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OR_FAIL(hipSetDevice(c->device));
     hipStream_t s = c->s_comp;
-    if ((rc = c->mg_runs.reserve(total))) return rc;
-    // the caller's arrays are read by asynchronous copies: whichever way this frame is left, they are waited for
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{s};
-    seb_run drun[SEB_MEM_MAX_RUNS] = {};
-    const void *dindex[SEB_MEM_MAX_RUNS] = {};
-    uint8_t *p = (uint8_t *)c->mg_runs.p;
-    for (uint32_t r = 0; r < num_runs; ++r) {
-        const seb_run &u = runs[r];
-        if (!u.n) continue;
-        seb_run &d = drun[r];
-        auto put = [&](const void *src, uint64_t bytes) -> const uint8_t * {  // null in, null out
-            uint8_t *at = p;
-            if (!src) return nullptr;
-            p += up(bytes);
-            return bytes && hipMemcpyAsync(at, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess ? nullptr : at;
-        };
-        d.n = u.n;
-        d.key_bytes = u.key_bytes;
-        d.keys = u.key_bytes ? put(u.keys, u.key_bytes) : nullptr;
-        d.key_off = (const uint64_t *)put(u.key_off, 8 * (u.n + 1));
-        d.val_off = (const uint64_t *)put(u.val_off, 8 * (u.n + 1));
-        d.deleted = put(u.deleted, u.n);
-        d.seq = (const uint64_t *)put(u.seq, 8 * u.n);
-        if ((u.key_bytes && !d.keys) || !d.key_off || !d.val_off || (u.deleted && !d.deleted) || (u.seq && !d.seq)) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s);
-            return fail(SEB_ERR_INTERNAL, "%s: run %u: a copy to the device failed", who, r);
-        }
-        dindex[r] = p;
-        p += up(run_index_bytes(u.n));
-        if ((rc = seb_dev_run_index(&d, (void *)dindex[r], run_index_bytes(u.n), s))) {
-            if (rc == SEB_ERR_INVALID) {  // the same words with the run's number
-                const std::string msg = last_error();
-                const size_t at = msg.find(": ");
-                return fail(rc, "%s: run %u: %s", who, r, at == std::string::npos ? msg.c_str() : msg.c_str() + at + 2);
-            }
-            return rc;
-        }
-    }
+    if ((rc = c->mg_runs.reserve(runs_upload_bytes(runs, nullptr, num_runs)))) return rc;
+    Drain drain{s};
+    RunUpload up;  // the values stay where they are: the answer is a location
+    if ((rc = runs_upload(runs, nullptr, nullptr, num_runs, (uint8_t *)c->mg_runs.p, &up, s, who))) return rc;
     if (kb->n == 0) return SEB_OK;
     return chunks_serial(c, kb, [&](const KeyBatch &dk, const Chunk &ch) -> int {
         const uint64_t n = dk.n;
-        // per key: vloc u64, seq u64, entry u32, vlen u32, status u8, run u8, each array 16-B aligned
-        const uint64_t o_seq = up(8 * n), o_ent = o_seq + up(8 * n), o_vlen = o_ent + up(4 * n), o_st = o_vlen + up(4 * n),
-                       o_run = o_st + up(n);
-        if ((rc = c->mg_out.reserve(o_run + up(n)))) return rc;
+        Carver out;  // per key: vloc u64, seq u64, entry u32, vlen u32, status u8, run u8
+        const uint64_t o_vloc = out.take(8 * n), o_seq = out.take(8 * n), o_ent = out.take(4 * n), o_vlen = out.take(4 * n),
+                       o_st = out.take(n), o_run = out.take(n);
+        if ((rc = c->mg_out.reserve(out.bytes()))) return rc;
         uint8_t *o = (uint8_t *)c->mg_out.p;
         const seb_keys dkeys{dk.data, dk.offsets, dk.n, dk.stride, 0};
-        if ((rc = seb_dev_runs_search(&dkeys, drun, dindex, num_runs, o + o_st, o + o_run, (uint32_t *)(o + o_ent),
-                                      (uint64_t *)o, (uint32_t *)(o + o_vlen), (uint64_t *)(o + o_seq), s)))
+        if ((rc = seb_dev_runs_search(&dkeys, up.drun, up.dindex, num_runs, o + o_st, o + o_run, (uint32_t *)(o + o_ent),
+                                      (uint64_t *)(o + o_vloc), (uint32_t *)(o + o_vlen), (uint64_t *)(o + o_seq), s)))
             return rc;
-        HIP_OR_FAIL(hipMemcpyAsync(status + ch.i0, o + o_st, n, hipMemcpyDeviceToHost, s));
-        if (run) HIP_OR_FAIL(hipMemcpyAsync(run + ch.i0, o + o_run, n, hipMemcpyDeviceToHost, s));
-        if (entry) HIP_OR_FAIL(hipMemcpyAsync(entry + ch.i0, o + o_ent, 4 * n, hipMemcpyDeviceToHost, s));
-        if (vloc) HIP_OR_FAIL(hipMemcpyAsync(vloc + ch.i0, o, 8 * n, hipMemcpyDeviceToHost, s));
-        if (vlen) HIP_OR_FAIL(hipMemcpyAsync(vlen + ch.i0, o + o_vlen, 4 * n, hipMemcpyDeviceToHost, s));
-        if (seq) HIP_OR_FAIL(hipMemcpyAsync(seq + ch.i0, o + o_seq, 8 * n, hipMemcpyDeviceToHost, s));
+        if ((rc = download(status + ch.i0, o + o_st, n, s)) || (rc = download(run ? run + ch.i0 : nullptr, o + o_run, n, s)) ||
+            (rc = download(entry ? entry + ch.i0 : nullptr, o + o_ent, 4 * n, s)) ||
+            (rc = download(vloc ? vloc + ch.i0 : nullptr, o + o_vloc, 8 * n, s)) ||
+            (rc = download(vlen ? vlen + ch.i0 : nullptr, o + o_vlen, 4 * n, s)) ||
+            (rc = download(seq ? seq + ch.i0 : nullptr, o + o_seq, 8 * n, s)))
+            return rc;
         return SEB_OK;
     });
 }

@@ -7,6 +7,7 @@
 #include "seb_block.h"
 #include "seb_blockids.h"
 #include "seb_host.h"
+#include "seb_stage.h"
 
 using namespace seb;
 
@@ -203,11 +204,10 @@ extern "C" int seb_search_blocks(seb_ctx *c, const seb_keys *kb, const uint32_t 
     }
     return chunks_serial(c, kb, [&](const KeyBatch &dk, const Chunk &ch) -> int {
         const uint64_t n = dk.n, ncell = n * (uint64_t)cap;
-        // per key: vloc u64, vlen u32, col u16, status u8, each array 16-B aligned
-        const uint64_t o_vlen = (8 * n + 15) & ~15ull, o_col = (o_vlen + 4 * n + 15) & ~15ull,
-                       o_st = (o_col + 2 * n + 15) & ~15ull;
+        Carver out;  // per key: vloc u64, vlen u32, col u16, status u8
+        const uint64_t o_vloc = out.take(8 * n), o_vlen = out.take(4 * n), o_col = out.take(2 * n), o_st = out.take(n);
         if ((rc = c->sb_bid.reserve(ncell * 4)) || (rc = c->sb_cells.reserve(ncell * 4)) ||
-            (rc = c->sb_out.reserve(o_st + n)))
+            (rc = c->sb_out.reserve(out.bytes())))
             return rc;
         uint8_t *o = (uint8_t *)c->sb_out.p;
         HIP_OR_FAIL(hipMemcpyAsync(c->sb_bid.p, bid + ch.i0 * cap, ncell * 4, hipMemcpyHostToDevice, c->s_comp));
@@ -215,13 +215,13 @@ extern "C" int seb_search_blocks(seb_ctx *c, const seb_keys *kb, const uint32_t 
                                          (const uint16_t *)c->sb_blen.p, num_blocks, (uint32_t *)c->sb_cells.p,
                                          c->s_comp));
         HIP_OR_FAIL(launch_resolve_rows((const uint32_t *)c->sb_cells.p, (const uint32_t *)c->sb_bid.p, n, cap, o + o_st,
-                                        (uint16_t *)(o + o_col), (uint64_t *)o, (uint32_t *)(o + o_vlen), c->s_comp));
-        HIP_OR_FAIL(hipMemcpyAsync(status + ch.i0, o + o_st, n, hipMemcpyDeviceToHost, c->s_comp));
-        if (col) HIP_OR_FAIL(hipMemcpyAsync(col + ch.i0, o + o_col, 2 * n, hipMemcpyDeviceToHost, c->s_comp));
-        if (vloc) HIP_OR_FAIL(hipMemcpyAsync(vloc + ch.i0, o, 8 * n, hipMemcpyDeviceToHost, c->s_comp));
-        if (vlen) HIP_OR_FAIL(hipMemcpyAsync(vlen + ch.i0, o + o_vlen, 4 * n, hipMemcpyDeviceToHost, c->s_comp));
-        if (cells)
-            HIP_OR_FAIL(hipMemcpyAsync(cells + ch.i0 * cap, c->sb_cells.p, ncell * 4, hipMemcpyDeviceToHost, c->s_comp));
+                                        (uint16_t *)(o + o_col), (uint64_t *)(o + o_vloc), (uint32_t *)(o + o_vlen), c->s_comp));
+        if ((rc = download(status + ch.i0, o + o_st, n, c->s_comp)) ||
+            (rc = download(col ? col + ch.i0 : nullptr, o + o_col, 2 * n, c->s_comp)) ||
+            (rc = download(vloc ? vloc + ch.i0 : nullptr, o + o_vloc, 8 * n, c->s_comp)) ||
+            (rc = download(vlen ? vlen + ch.i0 : nullptr, o + o_vlen, 4 * n, c->s_comp)) ||
+            (rc = download(cells ? cells + ch.i0 * cap : nullptr, c->sb_cells.p, ncell * 4, c->s_comp)))
+            return rc;
         return SEB_OK;
     });
 }
@@ -382,6 +382,7 @@ extern "C" int seb_sst_build(seb_ctx *c, const seb_keys *kb, const uint8_t *vals
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OR_FAIL(hipSetDevice(c->device));
     hipStream_t s = c->s_comp;
+    Drain drain{s};
     // the filter: NewBloomFilter(expected_keys, 0.01) + Add per key
     const uint64_t wb = seb_words_bytes(m);
     if ((rc = c->words.reserve(wb))) return rc;
@@ -393,41 +394,31 @@ extern "C" int seb_sst_build(seb_ctx *c, const seb_keys *kb, const uint8_t *vals
         HIP_OR_FAIL(hipStreamSynchronize(s));
         return SEB_OK;
     }
-    // the run on the device: key bytes, key offsets, value bytes, value offsets, deleted bytes
-    const uint64_t k0 = kb->offsets ? kb->offsets[0] : 0, k1 = kb->offsets ? kb->offsets[n] : n * (uint64_t)kb->stride;
-    const uint64_t v0 = val_off[0], v1 = val_off[n];
-    if ((v1 - v0) && !vals) return fail(SEB_ERR_INVALID, "%s: null vals", who);
-    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t a_keys = 0, a_koff = a_keys + up(k1 - k0), a_vals = a_koff + up(kb->offsets ? 8 * (n + 1) : 0),
-                   a_voff = a_vals + up(v1 - v0), a_del = a_voff + up(8 * (n + 1)), in_bytes = a_del + up(n);
+    // the run on the device, and the three sections
+    OpsOnDevice ops(kb, val_off);
+    if ((ops.v1 - ops.v0) && !vals) return fail(SEB_ERR_INVALID, "%s: null vals", who);
+    Carver in, outc;
+    ops.carve(in, kb, deleted != nullptr);
     const uint64_t ws_bytes = sst_ws_layout(n, 1).bytes;
-    const uint64_t a_index = up(sz.data_bytes), a_metao = a_index + up(sz.index_bytes), out_bytes = a_metao + up(sz.meta_bytes);
-    if ((rc = c->sst_in.reserve(in_bytes)) || (rc = c->sst_ws.reserve(ws_bytes, true)) || (rc = c->sst_out.reserve(out_bytes)))
+    const uint64_t a_data = outc.take(sz.data_bytes), a_index = outc.take(sz.index_bytes), a_metao = outc.take(sz.meta_bytes);
+    if ((rc = c->sst_in.reserve(in.bytes())) || (rc = c->sst_ws.reserve(ws_bytes, true)) ||
+        (rc = c->sst_out.reserve(outc.bytes())))
         return rc;
-    uint8_t *in = (uint8_t *)c->sst_in.p, *dout = (uint8_t *)c->sst_out.p;
-    if (k1 - k0) HIP_OR_FAIL(hipMemcpyAsync(in + a_keys, kb->data + k0, k1 - k0, hipMemcpyHostToDevice, s));
-    if (kb->offsets) HIP_OR_FAIL(hipMemcpyAsync(in + a_koff, kb->offsets, 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if (v1 - v0) HIP_OR_FAIL(hipMemcpyAsync(in + a_vals, vals + v0, v1 - v0, hipMemcpyHostToDevice, s));
-    HIP_OR_FAIL(hipMemcpyAsync(in + a_voff, val_off, 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if (deleted) HIP_OR_FAIL(hipMemcpyAsync(in + a_del, deleted, n, hipMemcpyHostToDevice, s));
-    KeyBatch dk{};  // offsets stay absolute: the data pointers are moved back by the first offset
-    dk.data = in + a_keys - k0;
-    dk.offsets = kb->offsets ? (const uint64_t *)(in + a_koff) : nullptr;
-    dk.n = n;
-    dk.stride = kb->stride;
+    uint8_t *dout = (uint8_t *)c->sst_out.p;
+    if ((rc = ops.upload(section(c->sst_in, 0), kb, vals, val_off, deleted, s))) return rc;
+    const KeyBatch dk = key_batch(&ops.keys);
     const uint64_t fbeg[2] = {0, n};
     seb_sst_sizes dsz;
-    HIP_OR_FAIL(launch_sst_plan(dk, (const uint64_t *)(in + a_voff), fbeg, 1, c->sst_ws.p, &dsz, s));
+    HIP_OR_FAIL(launch_sst_plan(dk, ops.val_off, fbeg, 1, c->sst_ws.p, &dsz, s));
     if (memcmp(&dsz, &sz, sizeof sz) != 0)
         return fail(SEB_ERR_INTERNAL, "%s: the device plan (%llu blocks, %llu index bytes) differs from the host's (%llu, %llu)",
                     who, (unsigned long long)dsz.num_blocks, (unsigned long long)dsz.index_bytes,
                     (unsigned long long)sz.num_blocks, (unsigned long long)sz.index_bytes);
-    HIP_OR_FAIL(launch_sst_encode(dk, in + a_vals - v0, (const uint64_t *)(in + a_voff),
-                                  deleted ? in + a_del : nullptr, 1, c->sst_ws.p, sz.num_blocks, sz.index_bytes,
-                                  sz.meta_bytes, dout, nullptr, dout + a_index, dout + a_metao, s));
-    HIP_OR_FAIL(hipMemcpyAsync(out, dout, sz.data_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(out + o_index, dout + a_index, sz.index_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(out + o_meta, dout + a_metao, sz.meta_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(launch_sst_encode(dk, ops.vals, ops.val_off, ops.deleted, 1, c->sst_ws.p, sz.num_blocks, sz.index_bytes,
+                                  sz.meta_bytes, dout + a_data, nullptr, dout + a_index, dout + a_metao, s));
+    if ((rc = download(out, dout + a_data, sz.data_bytes, s)) || (rc = download(out + o_index, dout + a_index, sz.index_bytes, s)) ||
+        (rc = download(out + o_meta, dout + a_metao, sz.meta_bytes, s)))
+        return rc;
     HIP_OR_FAIL(hipStreamSynchronize(s));
     return SEB_OK;
 }
@@ -632,49 +623,38 @@ extern "C" int seb_merge(seb_ctx *c, const uint8_t *pool, const uint16_t *blen, 
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OR_FAIL(hipSetDevice(c->device));
     hipStream_t s = c->s_comp;
-    auto up = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t pool_bytes = (uint64_t)num_blocks * SEB_BLOCK_BYTES, a_blen = pool_bytes, a_cnt = a_blen + up(2ull * num_blocks);
-    if ((rc = c->mrg_in.reserve(a_cnt + up(2ull * num_blocks)))) return rc;
-    uint8_t *in = (uint8_t *)c->mrg_in.p;
-    HIP_OR_FAIL(hipMemcpyAsync(in, pool, pool_bytes, hipMemcpyHostToDevice, s));
-    HIP_OR_FAIL(hipMemcpyAsync(in + a_blen, blen, 2ull * num_blocks, hipMemcpyHostToDevice, s));
+    Drain drain{s};
+    Carver inc;  // the pool, blen, each block's entry count
+    const uint64_t pool_bytes = (uint64_t)num_blocks * SEB_BLOCK_BYTES, a_pool = inc.take(pool_bytes),
+                   a_blen = inc.take(2ull * num_blocks), a_cnt = inc.take(2ull * num_blocks);
+    if ((rc = c->mrg_in.reserve(inc.bytes()))) return rc;
+    uint8_t *in = section(c->mrg_in, a_pool);
+    uint16_t *dblen = (uint16_t *)section(c->mrg_in, a_blen), *dcnt = (uint16_t *)section(c->mrg_in, a_cnt);
+    if ((rc = upload(in, pool, pool_bytes, s)) || (rc = upload((uint8_t *)dblen, blen, 2ull * num_blocks, s))) return rc;
     std::vector<uint64_t> run_entries;
     try {
         run_entries.resize(num_runs);
     } catch (const std::bad_alloc &) {
         return fail(SEB_ERR_NOMEM, "%s: out of host memory", who);
     }
-    if ((rc = seb_dev_merge_count(in, (const uint16_t *)(in + a_blen), num_blocks, run_begin, num_runs,
-                                  (uint16_t *)(in + a_cnt), run_entries.data(), s)))
-        return rc;
+    if ((rc = seb_dev_merge_count(in, dblen, num_blocks, run_begin, num_runs, dcnt, run_entries.data(), s))) return rc;
     uint64_t n = 0;
     for (uint64_t e : run_entries) n += e;
     if (n >= (1ull << 32)) return fail(SEB_ERR_INVALID, "%s: 2^32 entries or more", who);
     const uint64_t ws_bytes = merge_ws_layout(n, num_blocks, num_runs).bytes;
     if ((rc = c->mrg_ws.reserve(ws_bytes, true))) return rc;
-    if ((rc = seb_dev_merge_plan(in, (const uint16_t *)(in + a_blen), num_blocks, run_begin, num_runs,
-                                 (const uint16_t *)(in + a_cnt), flags, c->mrg_ws.p, ws_bytes, sizes, s)))
+    if ((rc = seb_dev_merge_plan(in, dblen, num_blocks, run_begin, num_runs, dcnt, flags, c->mrg_ws.p, ws_bytes, sizes, s)))
         return rc;
-    if (sizes->entries_out > entry_cap || sizes->key_bytes > key_cap || sizes->val_bytes > val_cap)
-        return fail(SEB_ERR_RANGE, "%s: a capacity is below its size (%llu entries, %llu key bytes, %llu value bytes); "
-                    "retry with *sizes", who, (unsigned long long)sizes->entries_out, (unsigned long long)sizes->key_bytes,
-                    (unsigned long long)sizes->val_bytes);
+    const RunDst dst{keys, key_cap, key_off, vals, val_cap, val_off, deleted, nullptr, entry_cap};
+    if ((rc = check_run_dst(who, dst, sizes->entries_out, sizes->key_bytes, sizes->val_bytes))) return rc;
     if (sizes->entries_in == 0) return SEB_OK;
-    const uint64_t no = sizes->entries_out;
-    if ((no && !deleted) || (sizes->key_bytes && !keys) || (sizes->val_bytes && !vals))
-        return fail(SEB_ERR_INVALID, "%s: null output", who);
-    const uint64_t o_koff = up(sizes->key_bytes), o_vals = o_koff + up(8 * (no + 1)), o_voff = o_vals + up(sizes->val_bytes),
-                   o_del = o_voff + up(8 * (no + 1)), out_bytes = o_del + up(no);
-    if ((rc = c->mrg_out.reserve(std::max<uint64_t>(out_bytes, 16)))) return rc;
+    const RunOut at(sizes->key_bytes, sizes->val_bytes, sizes->entries_out, false);
+    if ((rc = c->mrg_out.reserve(at.bytes))) return rc;
     uint8_t *o = (uint8_t *)c->mrg_out.p;
-    if ((rc = seb_dev_merge_emit(in, sizes, c->mrg_ws.p, ws_bytes, o, (uint64_t *)(o + o_koff), o + o_vals,
-                                 (uint64_t *)(o + o_voff), o + o_del, s)))
+    if ((rc = seb_dev_merge_emit(in, sizes, c->mrg_ws.p, ws_bytes, o, (uint64_t *)(o + at.koff), o + at.vals,
+                                 (uint64_t *)(o + at.voff), o + at.del, s)))
         return rc;
-    if (sizes->key_bytes) HIP_OR_FAIL(hipMemcpyAsync(keys, o, sizes->key_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(key_off, o + o_koff, 8 * (no + 1), hipMemcpyDeviceToHost, s));
-    if (sizes->val_bytes) HIP_OR_FAIL(hipMemcpyAsync(vals, o + o_vals, sizes->val_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(val_off, o + o_voff, 8 * (no + 1), hipMemcpyDeviceToHost, s));
-    if (no) HIP_OR_FAIL(hipMemcpyAsync(deleted, o + o_del, no, hipMemcpyDeviceToHost, s));
+    if ((rc = run_download(o, at, dst, s))) return rc;
     HIP_OR_FAIL(hipStreamSynchronize(s));
     return SEB_OK;
 }

@@ -4,6 +4,7 @@
 
 #include "seb_host.h"
 #include "seb_memwrite.h"
+#include "seb_stage.h"
 
 using namespace seb;
 
@@ -11,8 +12,6 @@ static_assert(sizeof(seb_fold_sizes) == sizeof(seb::FoldSizes) && sizeof(seb_fol
 static_assert(sizeof(seb_run) == sizeof(seb::Run), "seb_run layout");
 
 static const seb_fold_sizes kNoFold = {0, 0, 0, 0, 0, 0, 0, 0};
-
-static inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 // ------------------------------------------------ frame (lsm/lsm.go:97-137, lsm/wal.go:31-65)
 
@@ -302,107 +301,6 @@ extern "C" int seb_dev_runs_fold_emit(const seb_run *runs, const void *const *in
 
 // ------------------------------------------------ the host-buffer forms
 
-namespace {
-
-// the caller's arrays are read and written by asynchronous copies: whichever way a frame is left, they are waited for
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
-// Host runs into one device buffer: each run's key bytes, offsets, deleted bytes and sequences, its values where
-// `vals` is given, and its index (built and checked on the device).  drun / dindex / dvals: num_runs each.
-struct RunUpload {
-    seb_run drun[SEB_MEM_MAX_RUNS] = {};
-    const void *dindex[SEB_MEM_MAX_RUNS] = {};
-    const uint8_t *dvals[SEB_MEM_MAX_RUNS] = {};
-};
-
-uint64_t runs_upload_bytes(const seb_run *runs, const uint64_t *val_bytes, uint32_t num_runs) {
-    uint64_t total = 16;
-    for (uint32_t r = 0; r < num_runs; ++r) {
-        const seb_run &u = runs[r];
-        if (!u.n) continue;
-        total += up16(u.key_bytes) + 2 * up16(8 * (u.n + 1)) + up16(u.n) + up16(8 * u.n) + up16(run_index_bytes(u.n));
-        if (val_bytes) total += up16(val_bytes[r]);
-    }
-    return total;
-}
-
-int runs_upload(const seb_run *runs, const uint8_t *const *vals, const uint64_t *val_bytes, uint32_t num_runs, uint8_t *p,
-                RunUpload *up, hipStream_t s, const char *who) {
-    int rc;
-    for (uint32_t r = 0; r < num_runs; ++r) {
-        const seb_run &u = runs[r];
-        if (!u.n) continue;
-        seb_run &d = up->drun[r];
-        auto put = [&](const void *src, uint64_t bytes) -> const uint8_t * {  // null in, null out
-            uint8_t *at = p;
-            if (!src) return nullptr;
-            p += up16(bytes);
-            return bytes && hipMemcpyAsync(at, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess ? nullptr : at;
-        };
-        d.n = u.n;
-        d.key_bytes = u.key_bytes;
-        d.keys = u.key_bytes ? put(u.keys, u.key_bytes) : nullptr;
-        d.key_off = (const uint64_t *)put(u.key_off, 8 * (u.n + 1));
-        d.val_off = (const uint64_t *)put(u.val_off, 8 * (u.n + 1));
-        d.deleted = put(u.deleted, u.n);
-        d.seq = (const uint64_t *)put(u.seq, 8 * u.n);
-        bool vals_ok = true;
-        if (val_bytes && val_bytes[r]) {
-            up->dvals[r] = put(vals ? vals[r] : nullptr, val_bytes[r]);
-            vals_ok = up->dvals[r] != nullptr;
-        }
-        if ((u.key_bytes && !d.keys) || !d.key_off || !d.val_off || (u.deleted && !d.deleted) || (u.seq && !d.seq) || !vals_ok) {
-            (void)hipGetLastError();
-            return fail(SEB_ERR_INTERNAL, "%s: run %u: a null array, or a copy to the device failed", who, r);
-        }
-        up->dindex[r] = p;
-        p += up16(run_index_bytes(u.n));
-        if ((rc = seb_dev_run_index(&d, (void *)up->dindex[r], run_index_bytes(u.n), s))) {
-            if (rc == SEB_ERR_INVALID) {  // the same words with the run's number
-                const std::string msg = last_error();
-                const size_t at = msg.find(": ");
-                return fail(rc, "%s: run %u: %s", who, r, at == std::string::npos ? msg.c_str() : msg.c_str() + at + 2);
-            }
-            return rc;
-        }
-    }
-    return SEB_OK;
-}
-
-int check_host_runs(const seb_run *runs, uint32_t num_runs, uint32_t max_runs, const char *who) {
-    if (num_runs > max_runs || (num_runs && !runs)) return run_rc(-1, -1, false, 0, who);
-    for (uint32_t r = 0; r < num_runs; ++r) {
-        const seb_run &u = runs[r];
-        if (u.n >= (1ull << 32)) return run_rc(-5, (int)r, false, 0, who);
-        if (u.n && (!u.key_off || !u.val_off || (!u.keys && u.key_bytes))) return run_rc(-1, -1, false, 0, who);
-    }
-    return SEB_OK;
-}
-
-// the six arrays of a run on the device, in one buffer
-struct RunOut {
-    uint64_t koff, vals, voff, del, seq, bytes;  // keys at 0
-    RunOut(uint64_t key_bytes, uint64_t val_bytes, uint64_t n) {
-        koff = up16(key_bytes), vals = koff + up16(8 * (n + 1)), voff = vals + up16(val_bytes), del = voff + up16(8 * (n + 1));
-        seq = del + up16(n), bytes = seq + up16(8 * n);
-    }
-};
-
-int run_download(const uint8_t *o, const RunOut &at, uint64_t key_bytes, uint64_t val_bytes, uint64_t n, uint8_t *keys,
-                 uint64_t *key_off, uint8_t *vals, uint64_t *val_off, uint8_t *deleted, uint64_t *seq, hipStream_t s) {
-    if (key_bytes) HIP_OR_FAIL(hipMemcpyAsync(keys, o, key_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(key_off, o + at.koff, 8 * (n + 1), hipMemcpyDeviceToHost, s));
-    if (val_bytes) HIP_OR_FAIL(hipMemcpyAsync(vals, o + at.vals, val_bytes, hipMemcpyDeviceToHost, s));
-    HIP_OR_FAIL(hipMemcpyAsync(val_off, o + at.voff, 8 * (n + 1), hipMemcpyDeviceToHost, s));
-    if (n) HIP_OR_FAIL(hipMemcpyAsync(deleted, o + at.del, n, hipMemcpyDeviceToHost, s));
-    if (n && seq) HIP_OR_FAIL(hipMemcpyAsync(seq, o + at.seq, 8 * n, hipMemcpyDeviceToHost, s));
-    return SEB_OK;
-}
-
-}  // namespace
 
 extern "C" int seb_memtable_apply(seb_ctx *c, const seb_keys *kb, const uint8_t *vals, const uint64_t *val_off,
                                   const uint8_t *deleted, uint64_t first_seq, const seb_run *runs, uint32_t num_runs,
@@ -416,7 +314,8 @@ extern "C" int seb_memtable_apply(seb_ctx *c, const seb_keys *kb, const uint8_t 
     if (!c) return fail(SEB_ERR_INVALID, "%s: null ctx", who);
     if (!image_bytes || !sizes || !size_delta || !sequence || !run_key_off || !run_val_off) return frame_rc(-1, 0, who);
     if ((rc = check_ops(kb, val_off, who)) || (rc = validate_offsets(kb, who))) return rc;
-    if ((rc = check_host_runs(runs, num_runs, SEB_MEM_MAX_RUNS - 1, who))) return rc;
+    uint32_t bad_run = 0;
+    if ((rc = run_rc(check_host_runs(runs, num_runs, SEB_MEM_MAX_RUNS - 1, &bad_run), (int)bad_run, false, 0, who))) return rc;
     const uint64_t n = kb->n;
     *image_bytes = 0;
     *sizes = seb_replay_sizes{0, 0, 0, 0, 0, 0, 0, 0};
@@ -426,64 +325,47 @@ extern "C" int seb_memtable_apply(seb_ctx *c, const seb_keys *kb, const uint8_t 
     if (n == 0) return SEB_OK;
     if (val_off[n] < val_off[0]) return frame_rc(-3, 0, who);
     if (!kb->data && (kb->offsets || kb->stride)) return frame_rc(-1, 0, who);
-    // the ops' byte ranges go up as they are; the device pointers are set back by the first offset
-    const uint64_t k0 = kb->offsets ? kb->offsets[0] : 0, k1 = kb->offsets ? kb->offsets[n] : n * (uint64_t)kb->stride;
-    const uint64_t v0 = val_off[0], v1 = val_off[n];
-    if (v1 > v0 && !vals) return frame_rc(-1, 0, who);
+    OpsOnDevice ops(kb, val_off);
+    if (ops.v1 > ops.v0 && !vals) return frame_rc(-1, 0, who);
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OR_FAIL(hipSetDevice(c->device));
     hipStream_t s = c->s_comp;
-    const uint64_t i_koff = up16(k1 - k0), i_vals = i_koff + up16(kb->offsets ? 8 * (n + 1) : 0), i_voff = i_vals + up16(v1 - v0),
-                   i_del = i_voff + up16(8 * (n + 1)), i_rec = i_del + up16(deleted ? n : 0), i_delta = i_rec + up16(8 * (n + 1)),
-                   in_bytes = i_delta + 16;
-    if ((rc = c->mw_in.reserve(in_bytes))) return rc;
-    uint8_t *in = (uint8_t *)c->mw_in.p;
+    Carver in;  // the ops, their records' offsets, the size delta
+    ops.carve(in, kb, deleted != nullptr);
+    const uint64_t i_rec = in.take(8 * (n + 1)), i_delta = in.take(8);
+    if ((rc = c->mw_in.reserve(in.bytes()))) return rc;
     Drain drain{s};
-    if (k1 > k0) HIP_OR_FAIL(hipMemcpyAsync(in, kb->data + k0, k1 - k0, hipMemcpyHostToDevice, s));
-    if (kb->offsets) HIP_OR_FAIL(hipMemcpyAsync(in + i_koff, kb->offsets, 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if (v1 > v0) HIP_OR_FAIL(hipMemcpyAsync(in + i_vals, vals + v0, v1 - v0, hipMemcpyHostToDevice, s));
-    HIP_OR_FAIL(hipMemcpyAsync(in + i_voff, val_off, 8 * (n + 1), hipMemcpyHostToDevice, s));
-    if (deleted) HIP_OR_FAIL(hipMemcpyAsync(in + i_del, deleted, n, hipMemcpyHostToDevice, s));
-    const seb_keys dk{in - k0, kb->offsets ? (const uint64_t *)(in + i_koff) : nullptr, n, kb->stride, 0};
-    const uint8_t *dvals = in + i_vals - v0, *ddel = deleted ? in + i_del : nullptr;
-    const uint64_t *dvoff = (const uint64_t *)(in + i_voff);
-    uint64_t *drec = (uint64_t *)(in + i_rec);
+    if ((rc = ops.upload(section(c->mw_in, 0), kb, vals, val_off, deleted, s))) return rc;
+    uint64_t *drec = (uint64_t *)section(c->mw_in, i_rec);
     // frame and seal
-    if ((rc = seb_dev_wal_frame_plan(&dk, dvoff, ddel, drec, image_bytes, s))) return rc;
+    if ((rc = seb_dev_wal_frame_plan(&ops.keys, ops.val_off, ops.deleted, drec, image_bytes, s))) return rc;
     const uint64_t img = *image_bytes;
     if ((rc = c->mw_img.reserve(img))) return rc;
     uint8_t *dimg = (uint8_t *)c->mw_img.p;
-    if ((rc = seb_dev_wal_frame_emit(&dk, dvals, dvoff, ddel, first_seq, drec, dimg, img, s))) return rc;
+    if ((rc = seb_dev_wal_frame_emit(&ops.keys, ops.vals, ops.val_off, ops.deleted, first_seq, drec, dimg, img, s))) return rc;
     // replay: the batch's run
     const uint64_t ws_bytes = replay_ws_layout(n).bytes;
     if ((rc = c->mw_ws.reserve(ws_bytes, true))) return rc;
     if ((rc = seb_dev_wal_replay_plan(dimg, drec, n, c->mw_ws.p, ws_bytes, sizes, s))) return rc;
-    const uint64_t no = sizes->entries_out;
-    if (img > image_cap || no > entry_cap || sizes->key_bytes > key_cap || sizes->val_bytes > val_cap)
-        return fail(SEB_ERR_RANGE, "%s: a capacity is below its size (%llu image bytes, %llu entries, %llu key bytes, %llu value "
-                    "bytes); retry with *image_bytes and *sizes", who, (unsigned long long)img, (unsigned long long)no,
-                    (unsigned long long)sizes->key_bytes, (unsigned long long)sizes->val_bytes);
-    if (!image || (no && !run_deleted) || (sizes->key_bytes && !run_keys) || (sizes->val_bytes && !run_vals))
-        return fail(SEB_ERR_INVALID, "%s: null output", who);
-    HIP_OR_FAIL(hipMemcpyAsync(image, dimg, img, hipMemcpyDeviceToHost, s));
-    const RunOut at(sizes->key_bytes, sizes->val_bytes, no);
+    const RunDst dst{run_keys, key_cap, run_key_off, run_vals, val_cap, run_val_off, run_deleted, run_seq, entry_cap};
+    if ((rc = check_run_dst(who, dst, sizes->entries_out, sizes->key_bytes, sizes->val_bytes, &img, image_cap, image))) return rc;
+    if ((rc = download(image, dimg, img, s))) return rc;
+    const RunOut at(sizes->key_bytes, sizes->val_bytes, sizes->entries_out);
     if ((rc = c->mw_out.reserve(at.bytes))) return rc;
     uint8_t *o = (uint8_t *)c->mw_out.p;
     if ((rc = seb_dev_wal_replay_emit(dimg, drec, sizes, c->mw_ws.p, ws_bytes, o, (uint64_t *)(o + at.koff), o + at.vals,
                                       (uint64_t *)(o + at.voff), o + at.del, (uint64_t *)(o + at.seq), s)))
         return rc;
-    if ((rc = run_download(o, at, sizes->key_bytes, sizes->val_bytes, no, run_keys, run_key_off, run_vals, run_val_off,
-                           run_deleted, run_seq, s)))
-        return rc;
+    if ((rc = run_download(o, at, dst, s))) return rc;
     // the existing runs and their indexes, then the size delta
     if ((rc = c->mw_runs.reserve(runs_upload_bytes(runs, nullptr, num_runs)))) return rc;
     RunUpload up;
     if ((rc = runs_upload(runs, nullptr, nullptr, num_runs, (uint8_t *)c->mw_runs.p, &up, s, who))) return rc;
     const seb_run fresh{o, sizes->key_bytes, (const uint64_t *)(o + at.koff), (const uint64_t *)(o + at.voff), o + at.del,
-                        (const uint64_t *)(o + at.seq), no};
-    int64_t *ddelta = (int64_t *)(in + i_delta);
+                        (const uint64_t *)(o + at.seq), sizes->entries_out};
+    int64_t *ddelta = (int64_t *)section(c->mw_in, i_delta);
     if ((rc = seb_dev_run_size_delta(&fresh, up.drun, up.dindex, num_runs, ddelta, s))) return rc;
-    HIP_OR_FAIL(hipMemcpyAsync(size_delta, ddelta, 8, hipMemcpyDeviceToHost, s));
+    if ((rc = download(size_delta, ddelta, 8, s))) return rc;
     HIP_OR_FAIL(hipStreamSynchronize(s));
     return SEB_OK;
 }
@@ -498,7 +380,8 @@ extern "C" int seb_memtable_fold(seb_ctx *c, const seb_run *runs, const uint8_t 
     if (!sizes || !key_off || !val_off || (num_runs && !val_bytes)) return run_rc(-1, -1, false, 0, who);
     *sizes = kNoFold;
     key_off[0] = val_off[0] = 0;
-    if ((rc = check_host_runs(runs, num_runs, SEB_MEM_MAX_RUNS, who))) return rc;
+    uint32_t bad_run = 0;
+    if ((rc = run_rc(check_host_runs(runs, num_runs, SEB_MEM_MAX_RUNS, &bad_run), (int)bad_run, false, 0, who))) return rc;
     uint64_t entries = 0;
     for (uint32_t r = 0; r < num_runs; ++r) entries += runs[r].n;
     if (entries >= (1ull << 32)) return run_rc(-5, -1, false, 0, who);
@@ -513,22 +396,16 @@ extern "C" int seb_memtable_fold(seb_ctx *c, const seb_run *runs, const uint8_t 
     const uint64_t ws_bytes = fold_ws_layout(entries).bytes;
     if ((rc = c->mw_ws.reserve(ws_bytes, true))) return rc;
     if ((rc = seb_dev_runs_fold_plan(up.drun, up.dindex, val_bytes, num_runs, c->mw_ws.p, ws_bytes, sizes, s))) return rc;
-    const uint64_t no = sizes->entries_out;
-    if (no > entry_cap || sizes->key_bytes > key_cap || sizes->val_bytes > val_cap)
-        return fail(SEB_ERR_RANGE, "%s: a capacity is below its size (%llu entries, %llu key bytes, %llu value bytes); "
-                    "retry with *sizes", who, (unsigned long long)no, (unsigned long long)sizes->key_bytes,
-                    (unsigned long long)sizes->val_bytes);
-    if ((no && !deleted) || (sizes->key_bytes && !keys) || (sizes->val_bytes && !out_vals))
-        return fail(SEB_ERR_INVALID, "%s: null output", who);
-    const RunOut at(sizes->key_bytes, sizes->val_bytes, no);
+    const RunDst dst{keys, key_cap, key_off, out_vals, val_cap, val_off, deleted, seq, entry_cap};
+    if ((rc = check_run_dst(who, dst, sizes->entries_out, sizes->key_bytes, sizes->val_bytes))) return rc;
+    const RunOut at(sizes->key_bytes, sizes->val_bytes, sizes->entries_out);
     if ((rc = c->mw_out.reserve(at.bytes))) return rc;
     uint8_t *o = (uint8_t *)c->mw_out.p;
     if ((rc = seb_dev_runs_fold_emit(up.drun, up.dindex, up.dvals, val_bytes, num_runs, sizes, c->mw_ws.p, ws_bytes, o,
                                      (uint64_t *)(o + at.koff), o + at.vals, (uint64_t *)(o + at.voff), o + at.del,
                                      seq ? (uint64_t *)(o + at.seq) : nullptr, s)))
         return rc;
-    if ((rc = run_download(o, at, sizes->key_bytes, sizes->val_bytes, no, keys, key_off, out_vals, val_off, deleted, seq, s)))
-        return rc;
+    if ((rc = run_download(o, at, dst, s))) return rc;
     HIP_OR_FAIL(hipStreamSynchronize(s));
     return SEB_OK;
 }

@@ -549,21 +549,10 @@ class Ctx:
         deleted u8, sizes) of the merged run; caps = (key bytes, value bytes, entries) fixes the output
         capacities instead of retrying with the sizes a too small first call reports."""
         pool, blen, rb, nb, nr = _merge_host_args(pool, blen, run_begin)
-        kc, vc, ec = caps if caps is not None else (0, 0, 0)
         sz = seb_merge_sizes()
-        while True:
-            out = _merge_out(kc, vc, ec)
-            rc = lib().seb_merge(self._p, pool.ctypes.data if nb else None, blen.ctypes.data if nb else None, nb,
-                                 rb.ctypes.data if nr else None, nr, flags, out[0].ctypes.data, kc, out[1].ctypes.data,
-                                 out[2].ctypes.data, vc, out[3].ctypes.data, out[4].ctypes.data, ec, C.byref(sz))
-            if rc == -4 and caps is None and (sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
-                kc, vc, ec = sz.key_bytes, sz.val_bytes, sz.entries_out
-                continue
-            if rc < 0:  # SEB_ERR_RANGE fills the sizes: the exception carries them
-                err = SebError(rc, last_error())
-                err.sizes = sz.as_tuple()
-                raise err
-            return _merge_trim(out, sz)
+        return _retry_with_sizes(lambda *run: lib().seb_merge(
+            self._p, pool.ctypes.data if nb else None, blen.ctypes.data if nb else None, nb, rb.ctypes.data if nr else None, nr,
+            flags, *run, C.byref(sz)), caps, sz, seq=False)
 
     def wal_recover(self, image, caps: tuple[int, int, int] | None = None):
         """WAL.ReadAll + recoverFromWAL from host memory: the log image is scanned, verified and replayed.
@@ -572,21 +561,9 @@ class Ctx:
         with the sizes a too small first call reports.  A record that fails its CRC: SebError (INVALID, "CRC
         mismatch (record R)"); otherwise a truncated tail: SebError (SHORT)."""
         img = _wal_image_arg(image)
-        kc, vc, ec = caps if caps is not None else (0, 0, 0)
         sz = seb_replay_sizes()
-        while True:
-            out = _replay_out(kc, vc, ec)
-            rc = lib().seb_wal_recover(self._p, img.ctypes.data if img.size else None, img.size, out[0].ctypes.data, kc,
-                                       out[1].ctypes.data, out[2].ctypes.data, vc, out[3].ctypes.data, out[4].ctypes.data,
-                                       out[5].ctypes.data, ec, C.byref(sz))
-            if rc == -4 and caps is None and (sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
-                kc, vc, ec = sz.key_bytes, sz.val_bytes, sz.entries_out
-                continue
-            if rc < 0:  # SEB_ERR_RANGE fills the sizes: the exception carries them
-                err = SebError(rc, last_error())
-                err.sizes = sz.as_tuple()
-                raise err
-            return _replay_trim(out, sz)
+        return _retry_with_sizes(lambda *run: lib().seb_wal_recover(self._p, img.ctypes.data if img.size else None, img.size, *run,
+                                                                    C.byref(sz)), caps, sz)
 
     def memtable_get(self, keys, runs):
         """LSM.Get's memtable steps from host memory: `runs` are host_run()s, the active memtable first.
@@ -605,46 +582,19 @@ class Ctx:
         capacities instead of retrying with the sizes a too small first call reports."""
         kb, va, vo, de = _ops_host_args(keys, vals, val_off, deleted)
         arr = _run_array(list(runs))
-        ic, kc, vc, ec = caps if caps is not None else (0, 0, 0, 0)
         sz, img_bytes, delta, seq_after = seb_replay_sizes(), _u64(0), C.c_int64(0), _u64(0)
-        while True:
-            image = np.zeros(max(ic, 1), np.uint8)
-            out = _replay_out(kc, vc, ec)
-            rc = lib().seb_memtable_apply(self._p, kb.ref, va.ctypes.data, vo.ctypes.data, None if de is None else de.ctypes.data,
-                                          first_seq, arr, len(runs), image.ctypes.data, ic, C.byref(img_bytes),
-                                          out[0].ctypes.data, kc, out[1].ctypes.data, out[2].ctypes.data, vc, out[3].ctypes.data,
-                                          out[4].ctypes.data, out[5].ctypes.data, ec, C.byref(sz), C.byref(delta),
-                                          C.byref(seq_after))
-            if rc == -4 and caps is None and (img_bytes.value > ic or sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
-                ic, kc, vc, ec = img_bytes.value, sz.key_bytes, sz.val_bytes, sz.entries_out
-                continue
-            if rc < 0:  # SEB_ERR_RANGE fills the sizes: the exception carries them
-                err = SebError(rc, last_error())
-                err.sizes = sz.as_tuple()
-                err.image_bytes = img_bytes.value
-                raise err
-            return image[: img_bytes.value], _replay_trim(out, sz), delta.value, seq_after.value
+        image, run = _retry_with_sizes(lambda image, ic, *run: lib().seb_memtable_apply(
+            self._p, kb.ref, va.ctypes.data, vo.ctypes.data, None if de is None else de.ctypes.data, first_seq, arr, len(runs),
+            image, ic, C.byref(img_bytes), *run, C.byref(sz), C.byref(delta), C.byref(seq_after)), caps, sz, image_bytes=img_bytes)
+        return image, run, delta.value, seq_after.value
 
     def memtable_fold(self, runs, vals, caps=None):
         """Fold host_run()s (newest first; vals[r] = run r's value bytes) into the one run GetAllEntries() returns:
         (keys u8, key_off u64, vals u8, val_off u64, deleted u8, seq u64, fold sizes); caps = (key bytes, value
         bytes, entries)."""
         arr, vp, vb, keep = _fold_host_args(runs, vals)
-        kc, vc, ec = caps if caps is not None else (0, 0, 0)
         sz = seb_fold_sizes()
-        while True:
-            out = _replay_out(kc, vc, ec)
-            rc = lib().seb_memtable_fold(self._p, arr, vp, vb, len(runs), out[0].ctypes.data, kc, out[1].ctypes.data,
-                                         out[2].ctypes.data, vc, out[3].ctypes.data, out[4].ctypes.data, out[5].ctypes.data,
-                                         ec, C.byref(sz))
-            if rc == -4 and caps is None and (sz.entries_out > ec or sz.key_bytes > kc or sz.val_bytes > vc):
-                kc, vc, ec = sz.key_bytes, sz.val_bytes, sz.entries_out
-                continue
-            if rc < 0:
-                err = SebError(rc, last_error())
-                err.sizes = sz.as_tuple()
-                raise err
-            return _replay_trim(out, sz)
+        return _retry_with_sizes(lambda *run: lib().seb_memtable_fold(self._p, arr, vp, vb, len(runs), *run, C.byref(sz)), caps, sz)
 
     def probe_multi(self, keys, filters: list[tuple[np.ndarray, int, int]]) -> np.ndarray:
         kb = as_keys(keys)
@@ -1274,14 +1224,44 @@ def _merge_host_args(pool, blen, run_begin):
     return pool, blen, rb, nb, nr
 
 
-def _merge_out(key_bytes: int, val_bytes: int, entries: int):
-    return (np.zeros(max(key_bytes, 1), np.uint8), np.zeros(entries + 1, np.uint64), np.zeros(max(val_bytes, 1), np.uint8),
-            np.zeros(entries + 1, np.uint64), np.zeros(max(entries, 1), np.uint8))
+def _run_out(key_bytes: int, val_bytes: int, entries: int, seq: bool = True):
+    """A sorted run's output arrays: keys u8, key_off u64, vals u8, val_off u64, deleted u8 and, with seq, seq u64."""
+    out = (np.zeros(max(key_bytes, 1), np.uint8), np.zeros(entries + 1, np.uint64), np.zeros(max(val_bytes, 1), np.uint8),
+           np.zeros(entries + 1, np.uint64), np.zeros(max(entries, 1), np.uint8))
+    return out + (np.zeros(max(entries, 1), np.uint64),) if seq else out
 
 
-def _merge_trim(out, sz):
+def _run_trim(out, sz, seq: bool = True):
+    """_run_out's arrays cut to the sizes, and the sizes."""
     n = sz.entries_out
-    return out[0][: sz.key_bytes], out[1][: n + 1], out[2][: sz.val_bytes], out[3][: n + 1], out[4][:n], sz.as_tuple()
+    run = (out[0][: sz.key_bytes], out[1][: n + 1], out[2][: sz.val_bytes], out[3][: n + 1], out[4][:n])
+    return run + ((out[5][:n],) if seq else ()) + (sz.as_tuple(),)
+
+
+def _retry_with_sizes(call, caps, sz, seq: bool = True, image_bytes=None):
+    """A host-buffer form that returns a sorted run, called with output capacities caps = ([image bytes,] key bytes,
+    value bytes, entries): call([image, its capacity,] the run's arrays and capacities in the forms' order) -> rc.
+    Without caps a call that reports SEB_ERR_RANGE is repeated with the sizes it filled (sz, and image_bytes where the
+    form returns an image); any other error is raised with the sizes attached.  Returns the trimmed run[, after the image]."""
+    fixed = caps is not None
+    caps = tuple(caps) if fixed else (0,) * (3 if image_bytes is None else 4)
+    while True:
+        kc, vc, ec = caps[-3:]
+        out = _run_out(kc, vc, ec, seq)
+        p = [a.ctypes.data for a in out]
+        image = None if image_bytes is None else np.zeros(max(caps[0], 1), np.uint8)
+        rc = call(*(() if image is None else (image.ctypes.data, caps[0])), p[0], kc, p[1], p[2], vc, p[3], *p[4:], ec)
+        need = (() if image is None else (image_bytes.value,)) + (sz.key_bytes, sz.val_bytes, sz.entries_out)
+        if rc == -4 and not fixed and any(n > c for n, c in zip(need, caps)):
+            caps = need
+            continue
+        if rc < 0:  # SEB_ERR_RANGE fills the sizes: the exception carries them
+            err = SebError(rc, last_error())
+            err.sizes = sz.as_tuple()
+            if image is not None:
+                err.image_bytes = image_bytes.value
+            raise err
+        return _run_trim(out, sz, seq) if image is None else (image[: image_bytes.value], _run_trim(out, sz, seq))
 
 
 def merge_plan(pool, blen, run_begin, flags: int = 0) -> tuple[int, int, int, int, int, int]:
@@ -1299,11 +1279,11 @@ def merge_emit(pool, blen, run_begin, flags: int = 0, sizes=None):
     sizes default to merge_plan's."""
     pool, blen, rb, nb, nr = _merge_host_args(pool, blen, run_begin)
     sz = seb_merge_sizes(*(merge_plan(pool, blen, rb, flags) if sizes is None else sizes))
-    out = _merge_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
+    out = _run_out(sz.key_bytes, sz.val_bytes, sz.entries_out, seq=False)
     check(lib().seb_merge_emit(pool.ctypes.data if nb else None, blen.ctypes.data if nb else None,
                                rb.ctypes.data if nr else None, nr, flags, out[0].ctypes.data, out[1].ctypes.data,
                                out[2].ctypes.data, out[3].ctypes.data, out[4].ctypes.data, C.byref(sz)))
-    return _merge_trim(out, sz)
+    return _run_trim(out, sz, seq=False)
 
 
 def _run_begin(run_begin):
@@ -1378,16 +1358,6 @@ def _replay_host_args(image, rec_off):
     return img, off, max(off.size - 1, 0)
 
 
-def _replay_out(key_bytes: int, val_bytes: int, entries: int):
-    return _merge_out(key_bytes, val_bytes, entries) + (np.zeros(max(entries, 1), np.uint64),)
-
-
-def _replay_trim(out, sz):
-    n = sz.entries_out
-    return (out[0][: sz.key_bytes], out[1][: n + 1], out[2][: sz.val_bytes], out[3][: n + 1], out[4][:n], out[5][:n],
-            sz.as_tuple())
-
-
 def wal_replay_plan(image, rec_off) -> tuple[int, int, int, int, int, int, int, int]:
     """The host half's plan: (records_in, entries_out, key_bytes, val_bytes, overwritten, tombstones,
     max_sequence, memtable_size) of the replay of records [rec_off[i], rec_off[i+1]) of the image.  A record
@@ -1403,11 +1373,11 @@ def wal_replay_emit(image, rec_off, sizes=None):
     sorted run; sizes default to wal_replay_plan's."""
     img, off, n = _replay_host_args(image, rec_off)
     sz = seb_replay_sizes(*(wal_replay_plan(img, off) if sizes is None else sizes))
-    out = _replay_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
+    out = _run_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
     check(lib().seb_wal_replay_emit(img.ctypes.data if n else None, off.ctypes.data if n else None, n, out[0].ctypes.data,
                                     out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, out[4].ctypes.data,
                                     out[5].ctypes.data, C.byref(sz)))
-    return _replay_trim(out, sz)
+    return _run_trim(out, sz)
 
 
 def dev_wal_replay_workspace_size(n: int) -> int:
@@ -1952,10 +1922,10 @@ def runs_fold(runs, vals, sizes=None):
     runs add up to; sizes default to runs_fold_plan's."""
     arr, vp, vb, keep = _fold_host_args(runs, vals)
     sz = seb_fold_sizes(*(runs_fold_plan(runs, vals) if sizes is None else sizes))
-    out = _replay_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
+    out = _run_out(sz.key_bytes, sz.val_bytes, sz.entries_out)
     check(lib().seb_runs_fold_emit(arr, vp, vb, len(runs), out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data,
                                    out[3].ctypes.data, out[4].ctypes.data, out[5].ctypes.data, C.byref(sz)))
-    return _replay_trim(out, sz)
+    return _run_trim(out, sz)
 
 
 def dev_runs_fold_workspace_size(entries: int) -> int:
