@@ -1369,8 +1369,8 @@ int seb_hidx_compact(seb_ctx *ctx, const uint8_t *dev_pool, uint64_t pool_bytes,
 /* ------------- B-tree, read side: a page-file image checked, Get for a key batch ---- */
 /* The reference's third engine (btree/) is a page-based B+-tree in one file.  This group is its read side: what
  * readMetadata (btree/pager.go:142-164) makes of the file, a structural check of every page, and what Get
- * (btree/btree.go:232-280) answers from the pages, for a key batch.  Range scans, the write side (Put, splits, Delete,
- * merges), the WAL's replay and the pager's cache stay with the caller, who hands over the image that Sync wrote, with
+ * (btree/btree.go:232-280) answers from the pages, for a key batch.  Range scans are the next group; the write side (Put,
+ * splits, Delete, merges), the WAL's replay and the pager's cache stay with the caller, who hands over the image that Sync wrote, with
  * any WAL already applied.
  *
  * Layout (btree/page.go:9-44): page p at byte p * SEB_BT_PAGE_BYTES; every integer big-endian.  Page 0: magic,
@@ -1453,6 +1453,103 @@ int seb_dev_bt_get(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta
  * cap is below the pages' bytes (*meta is filled, nothing is uploaded). */
 int seb_bt_load(seb_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *dev_image, uint64_t cap, uint8_t *dev_kind,
                 uint8_t *dev_level, seb_bt_meta *meta, seb_bt_stats *stats);
+
+/* ------------- B-tree, range scans: a leaf directory per image, Scan for a batch of ranges ---- */
+/* BTree.Scan(startKey, endKey) (btree/btree.go, btree/iterator.go) for a batch of ranges [start, end).  The reference's
+ * Iterator is serial: seek, then cell by cell and leaf by leaf along RightPtr.  Here the leaves' key order is derived
+ * from the tree top-down, ONCE PER IMAGE after the check, into a LEAF DIRECTORY; the chain is only checked against that
+ * order and never followed.  A range then costs two seeks (seb_bt_get's walk) and arithmetic on global key positions,
+ * and every output entry is located on its own, so the work balances by entries and not by ranges.
+ *
+ * THE DIRECTORY: one flat buffer of seb_bt_dir_bytes(num_pages) bytes, 8-byte aligned, little-endian; the host form and
+ * the device form write the same bytes.  Its arrays' offsets depend on num_pages alone (each has room for num_pages
+ * leaves):
+ *   [0, 32)                           u32 SEB_BT_DIR_MAGIC, u32 num_pages, u32 root, u32 leaves L, u64 keys, u32 depth, u32 0
+ *   32                                leaf[num_pages] u32: the reachable leaves' page ids in key order; 0 from entry L on
+ *   F = (32 + 4 num_pages + 7) & ~7   first[num_pages + 1] u64: the exclusive prefix sum of the leaves' numCells, first[L]
+ *                                     = keys; 0 behind it
+ *   F + 8 num_pages + 8               ord[num_pages] u32: a page's position in leaf[], SEB_BT_NO_PAGE for a page that is no
+ *                                     listed leaf
+ * It is built level by level from the root: level 0 is [root]; a level's pages hand on their children, the right
+ * pointer FIRST (it is the leftmost child), then the cells' children in directory order; the first level that holds
+ * leaves is leaf[].  kind and level are seb_bt_check's arrays, both required.
+ * REFUSALS, each SEB_ERR_INVALID with "page P" in seb_last_error, tested in this order; the header is then zero and
+ * nothing in the buffer means anything:
+ *   the root lies outside [1, num_pages);
+ *   per level r, the listed page at the least position that is bad by the check (or outside the image), else whose
+ *     level is not r (a self-pointer, a page with parents at two levels), else whose kind differs from the kind of the
+ *     level's first page (leaves at two levels);
+ *   level SEB_BT_MAX_DEPTH - 1 holds internal pages (deeper than Get walks): names the level's first page;
+ *   a level's children number more than num_pages (not a tree; it bounds the lists on a DAG): the level's first page;
+ *   a leaf listed twice: the least such page id;
+ *   the chain: the leaf at the least position i with RightPtr(leaf[i]) != leaf[i + 1], or != 0 on the last leaf;
+ *   the order: the leaf at the least position whose last key is not strictly below the first key of the next
+ *     NON-EMPTY leaf.
+ * Chain and order make the position arithmetic below equal to a chain-following iterator on every accepted image.
+ * seb_dev_bt_dir_build: device pointers (image, kind, level at any alignment); the workspace is
+ * seb_dev_bt_dir_workspace_size(num_pages) bytes of device memory, 16-byte aligned, opaque; SYNCHRONISES (a read-back
+ * per level, as the check); *info is HOST memory.
+ *
+ * SCAN.  starts / ends: two seb_keys of equal n; range r is [start_r, end_r).  An empty start means from the first key,
+ * an empty end means unbounded (the reference's nil endKey; a caller with a non-nil empty endKey, for which the
+ * reference yields nothing, answers that itself).  limit (0: none) caps each range's entries.  A bound is sought as
+ * seb_bt_get walks; (leaf, pos) becomes the global position first[ord[leaf]] + pos; count = min(limit, max(0, last -
+ * first)).  range_status[r] = 0, or SEB_GET_ERROR with no entries where a seek ended in ERROR or at a page the
+ * directory does not list.  range_off[0..n] = the exclusive scan of the counts.  Per output entry e of range r, global
+ * position g = first_r + (e - range_off[r]): status[e] = SEB_GET_FOUND, source[e] = 1, kloc / klen and vloc / vlen = the
+ * key's and the value's place in the image; SEB_GET_ERROR with zero lengths where the cell no longer parses (the image
+ * changed after the directory was built).  These arrays are what seb_dev_get_values_plan / _emit take with the image
+ * as `pool` and num_runs = 0: one gather over (kloc, klen) gives key_off + keys, one over (vloc, vlen) val_off + values,
+ * and range r's entries are a sorted run in the builder's input layout.
+ * SEB_ERR_RANGE: 2^32 entries or more (the gather's limit; sizes->entries says how many).  SEB_ERR_INVALID: dir's
+ * header is not this image's (magic, num_pages, root), a NULL or misaligned pointer, starts->n != ends->n.
+ * Host form seb_bt_scan: all host memory; also the dense keys and values.  entry_cap / key_cap / val_cap below the
+ * need: SEB_ERR_RANGE with *sizes filled for a retry (range_status and range_off are written all the same); NULL entry
+ * outputs with caps of 0 only size.  It is the reference for the device form.
+ * Device: seb_dev_bt_scan_plan (SYNCHRONISES; fills *sizes: ranges, entries; key_bytes and val_bytes stay 0, the
+ * gathers size them) keeps range_off and first_r in the workspace (seb_dev_bt_scan_workspace_size(ranges) bytes, 8-byte
+ * aligned, opaque; 0 for 2^32 ranges or more).  seb_dev_bt_scan_cells (not synchronised; the same image, dir and
+ * workspace) writes range_off[0..ranges] and the six entry arrays, one lane per ENTRY; it writes nothing where the
+ * workspace holds another plan.  Bounds, whatever the image or the directory holds: every ord / leaf / first index is
+ * tested against L <= num_pages, every page id against num_pages, both bisections are counted, and nothing is written
+ * outside ranges / ranges + 1 / entries elements.
+ *
+ * DEPARTURES from btree/iterator.go.  (1) Empty start: the reference's seek descends by CellAt(0).Child, which skips
+ * the subtree under RightPtr (the leftmost, by findChild and GetChildPageID's own comment) at every level, and returns
+ * an empty scan on an internal page without cells; here an empty start begins at the first key of the tree (on a
+ * root-leaf tree both agree).  (2) An empty leaf inside the chain: the reference's Next moves to it and fails in
+ * CellAt(0), or with a nil end hands out a nil key; here it contributes no entry and the scan goes on.  (3) Images the
+ * directory refuses are still iterated by the reference; among them are the images its own splitInternal produces from
+ * depth 3 on (the two leftmost children change places), which fail both the chain and the order rule. */
+#define SEB_BT_DIR_MAGIC 0x42544452u
+typedef struct seb_bt_dir_info {
+    uint64_t leaves, keys;    /* L, first[L] */
+    uint32_t depth, reserved; /* levels, the leaves' included */
+} seb_bt_dir_info;
+typedef struct seb_bt_scan_sizes {
+    uint64_t ranges, entries;
+    uint64_t key_bytes, val_bytes; /* host form only */
+} seb_bt_scan_sizes;
+uint64_t seb_bt_dir_bytes(uint32_t num_pages);
+int seb_bt_dir_build(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *kind,
+                     const uint8_t *level, uint8_t *dir, seb_bt_dir_info *info);
+int seb_bt_scan(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *dir,
+                const seb_keys *starts, const seb_keys *ends, uint64_t limit, uint8_t *range_status, uint64_t *range_off,
+                uint8_t *status, uint8_t *source, uint64_t *kloc, uint32_t *klen, uint64_t *vloc, uint32_t *vlen,
+                uint64_t entry_cap, uint64_t *key_off, uint8_t *keys, uint64_t key_cap, uint64_t *val_off, uint8_t *vals,
+                uint64_t val_cap, seb_bt_scan_sizes *sizes);
+uint64_t seb_dev_bt_dir_workspace_size(uint32_t num_pages);
+int seb_dev_bt_dir_build(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *kind,
+                         const uint8_t *level, uint8_t *dir, void *workspace, uint64_t workspace_bytes,
+                         seb_bt_dir_info *info, void *stream);
+uint64_t seb_dev_bt_scan_workspace_size(uint64_t ranges);
+int seb_dev_bt_scan_plan(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *dir,
+                         const seb_keys *starts, const seb_keys *ends, uint64_t limit, uint8_t *range_status,
+                         void *workspace, uint64_t workspace_bytes, seb_bt_scan_sizes *sizes, void *stream);
+int seb_dev_bt_scan_cells(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *dir,
+                          const seb_bt_scan_sizes *sizes, const void *workspace, uint64_t workspace_bytes,
+                          uint64_t *range_off, uint8_t *status, uint8_t *source, uint64_t *kloc, uint32_t *klen,
+                          uint64_t *vloc, uint32_t *vlen, void *stream);
 
 #ifdef __cplusplus
 }

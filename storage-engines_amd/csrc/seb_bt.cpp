@@ -119,3 +119,153 @@ extern "C" int seb_bt_load(seb_ctx *c, const uint8_t *image, uint64_t image_byte
     if (rc) (void)hipStreamSynchronize(st);  // the caller's image is not read after the return
     return rc;
 }
+
+// ------------------------------------------------ range scans: the leaf directory, batched Scan
+
+static_assert(sizeof(seb_bt_dir_info) == sizeof(seb::BtDirInfo) && sizeof(seb_bt_dir_info) == 24, "seb_bt_dir_info layout");
+static_assert(sizeof(seb_bt_scan_sizes) == sizeof(seb::BtScanSizes) && sizeof(seb_bt_scan_sizes) == 32, "seb_bt_scan_sizes layout");
+static_assert(SEB_BT_DIR_MAGIC == seb::kBtDirMagic, "the directory's magic");
+
+static int dir_refused(int rule, uint32_t page, const char *who) {
+    return fail(SEB_ERR_INVALID, "%s: page %u: %s", who, page, bt_dir_rule_text(rule));
+}
+
+static int scan_rc(int rc, const seb_bt_scan_sizes *sz, const char *who) {
+    switch (rc) {
+    case -6:
+        return fail(SEB_ERR_INVALID, "%s: dir is not the directory of this image", who);
+    case -7:
+        return fail(SEB_ERR_RANGE, "%s: a cap is below the scan's %llu entries, %llu key bytes, %llu value bytes; retry with *sizes",
+                    who, (unsigned long long)sz->entries, (unsigned long long)sz->key_bytes, (unsigned long long)sz->val_bytes);
+    case -8:
+        return fail(SEB_ERR_RANGE, "%s: the ranges hold 2^32 entries or more (%llu)", who, (unsigned long long)sz->entries);
+    default:
+        return bt_rc(rc, who);
+    }
+}
+
+extern "C" uint64_t seb_bt_dir_bytes(uint32_t num_pages) { return seb::bt_dir_bytes(num_pages); }
+
+extern "C" int seb_bt_dir_build(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *kind,
+                                const uint8_t *level, uint8_t *dir, seb_bt_dir_info *info) {
+    const char *who = "seb_bt_dir_build";
+    if (!meta) return bt_rc(-1, who);
+    if ((uintptr_t)dir & 7) return fail(SEB_ERR_INVALID, "%s: dir is not 8-byte aligned", who);
+    int rule = 0;
+    uint32_t page = 0;
+    const int rc = seb::bt_dir_build(image, image_bytes, meta_of(meta), kind, level, dir, reinterpret_cast<BtDirInfo *>(info), &rule, &page);
+    return rc == -5 ? dir_refused(rule, page, who) : bt_rc(rc, who);
+}
+
+static BtKeys host_keys(const seb_keys *k) { return BtKeys{k->data, k->offsets, k->n, k->stride}; }
+
+extern "C" int seb_bt_scan(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *dir,
+                           const seb_keys *starts, const seb_keys *ends, uint64_t limit, uint8_t *range_status, uint64_t *range_off,
+                           uint8_t *status, uint8_t *source, uint64_t *kloc, uint32_t *klen, uint64_t *vloc, uint32_t *vlen,
+                           uint64_t entry_cap, uint64_t *key_off, uint8_t *keys, uint64_t key_cap, uint64_t *val_off, uint8_t *vals,
+                           uint64_t val_cap, seb_bt_scan_sizes *sizes) {
+    const char *who = "seb_bt_scan";
+    int rc;
+    if (!meta || !sizes) return bt_rc(-1, who);
+    if ((rc = check_keys(starts, who)) || (rc = validate_offsets(starts, who)) || (rc = check_keys(ends, who)) ||
+        (rc = validate_offsets(ends, who)))
+        return rc;
+    if (starts->n != ends->n) return fail(SEB_ERR_INVALID, "%s: %llu starts, %llu ends", who, (unsigned long long)starts->n,
+                                          (unsigned long long)ends->n);
+    if ((uintptr_t)dir & 7) return fail(SEB_ERR_INVALID, "%s: dir is not 8-byte aligned", who);
+    const BtScanOut out{range_status, range_off, status, source, kloc, vloc, klen, vlen, entry_cap, key_off, val_off, keys, vals, key_cap, val_cap};
+    rc = seb::bt_scan(image, image_bytes, meta_of(meta), dir, host_keys(starts), host_keys(ends), limit, out,
+                      reinterpret_cast<BtScanSizes *>(sizes));
+    return scan_rc(rc, sizes, who);
+}
+
+extern "C" uint64_t seb_dev_bt_dir_workspace_size(uint32_t num_pages) { return bt_dir_ws_bytes(num_pages); }
+
+extern "C" int seb_dev_bt_dir_build(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *kind,
+                                    const uint8_t *level, uint8_t *dir, void *workspace, uint64_t workspace_bytes,
+                                    seb_bt_dir_info *info, void *stream) {
+    const char *who = "seb_dev_bt_dir_build";
+    enter();
+    int rc;
+    if ((rc = check_image(image, image_bytes, meta, who))) return rc;
+    if (!dir || !info || !workspace || (meta->num_pages && (!kind || !level))) return bt_rc(-1, who);
+    if (((uintptr_t)dir & 7) || ((uintptr_t)workspace & 15))
+        return fail(SEB_ERR_INVALID, "%s: dir is not 8-byte aligned or the workspace not 16-byte aligned", who);
+    if (workspace_bytes < bt_dir_ws_bytes(meta->num_pages))
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes for %u pages", who, (unsigned long long)workspace_bytes,
+                    (unsigned long long)bt_dir_ws_bytes(meta->num_pages), meta->num_pages);
+    int rule = 0;
+    uint32_t page = 0;
+    HIP_OR_FAIL(launch_bt_dir_build(image, meta->num_pages, meta->root, kind, level, dir, workspace, reinterpret_cast<BtDirInfo *>(info),
+                                    &rule, &page, (hipStream_t)stream));
+    return rule ? dir_refused(rule, page, who) : SEB_OK;
+}
+
+extern "C" uint64_t seb_dev_bt_scan_workspace_size(uint64_t ranges) { return ranges >= (1ull << 32) ? 0 : bt_scan_ws_bytes(ranges); }
+
+// what the plan and the cells test alike
+static int scan_args(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *dir, uint64_t ranges,
+                     const void *workspace, uint64_t workspace_bytes, const char *who) {
+    int rc;
+    if ((rc = check_image(image, image_bytes, meta, who))) return rc;
+    if (ranges >= (1ull << 32)) return fail(SEB_ERR_INVALID, "%s: 2^32 ranges or more", who);
+    if (!dir) return bt_rc(-1, who);
+    if ((uintptr_t)dir & 7) return fail(SEB_ERR_INVALID, "%s: dir is not 8-byte aligned", who);
+    if (ranges == 0) return SEB_OK;
+    if (!workspace) return bt_rc(-1, who);
+    if ((uintptr_t)workspace & 7) return fail(SEB_ERR_INVALID, "%s: the workspace is not 8-byte aligned", who);
+    if (workspace_bytes < bt_scan_ws_bytes(ranges))
+        return fail(SEB_ERR_INVALID, "%s: workspace %llu < %llu bytes for %llu ranges", who, (unsigned long long)workspace_bytes,
+                    (unsigned long long)bt_scan_ws_bytes(ranges), (unsigned long long)ranges);
+    return SEB_OK;
+}
+
+extern "C" int seb_dev_bt_scan_plan(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *dir,
+                                    const seb_keys *starts, const seb_keys *ends, uint64_t limit, uint8_t *range_status,
+                                    void *workspace, uint64_t workspace_bytes, seb_bt_scan_sizes *sizes, void *stream) {
+    const char *who = "seb_dev_bt_scan_plan";
+    enter();
+    int rc;
+    if (!sizes) return bt_rc(-1, who);
+    *sizes = seb_bt_scan_sizes{0, 0, 0, 0};
+    if ((rc = check_keys(starts, who)) || (rc = check_keys(ends, who))) return rc;
+    if (starts->n != ends->n) return fail(SEB_ERR_INVALID, "%s: %llu starts, %llu ends", who, (unsigned long long)starts->n,
+                                          (unsigned long long)ends->n);
+    sizes->ranges = starts->n;
+    if ((rc = scan_args(image, image_bytes, meta, dir, starts->n, workspace, workspace_bytes, who))) return rc;
+    if (((uintptr_t)starts->offsets & 7) || ((uintptr_t)ends->offsets & 7)) return fail(SEB_ERR_INVALID, "%s: offsets not 8-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t head[32];
+    uint32_t leaves;
+    uint64_t keys;
+    HIP_OR_FAIL(bt_scan_read_dir(dir, head, s));
+    if (!bt_dir_header_ok(head, meta_of(meta), &leaves, &keys)) return scan_rc(-6, sizes, who);
+    if (starts->n == 0) return SEB_OK;
+    if (!range_status) return fail(SEB_ERR_INVALID, "%s: null range_status", who);
+    HIP_OR_FAIL(launch_bt_scan_plan(image, meta->num_pages, meta->root, dir, key_batch(starts), key_batch(ends), limit, workspace,
+                                    range_status, &sizes->entries, s));
+    return sizes->entries >> 32 ? scan_rc(-8, sizes, who) : SEB_OK;
+}
+
+extern "C" int seb_dev_bt_scan_cells(const uint8_t *image, uint64_t image_bytes, const seb_bt_meta *meta, const uint8_t *dir,
+                                     const seb_bt_scan_sizes *sizes, const void *workspace, uint64_t workspace_bytes,
+                                     uint64_t *range_off, uint8_t *status, uint8_t *source, uint64_t *kloc, uint32_t *klen,
+                                     uint64_t *vloc, uint32_t *vlen, void *stream) {
+    const char *who = "seb_dev_bt_scan_cells";
+    enter();
+    int rc;
+    if (!sizes) return bt_rc(-1, who);
+    if ((rc = scan_args(image, image_bytes, meta, dir, sizes->ranges, workspace, workspace_bytes, who))) return rc;
+    if (sizes->entries >> 32) return scan_rc(-8, sizes, who);
+    if (!range_off || (sizes->entries && (!status || !source || !kloc || !klen || !vloc || !vlen))) return bt_rc(-1, who);
+    if (((uintptr_t)range_off & 7) || ((uintptr_t)kloc & 7) || ((uintptr_t)vloc & 7) || ((uintptr_t)klen & 3) || ((uintptr_t)vlen & 3))
+        return fail(SEB_ERR_INVALID, "%s: range_off, kloc or vloc not 8-byte aligned, or klen or vlen not 4-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (sizes->ranges == 0) {
+        HIP_OR_FAIL(hipMemsetAsync(range_off, 0, 8, s));
+        return SEB_OK;
+    }
+    HIP_OR_FAIL(launch_bt_scan_cells(image, meta->num_pages, meta->root, dir, sizes->ranges, sizes->entries, workspace, range_off, status,
+                                     source, kloc, klen, vloc, vlen, s));
+    return SEB_OK;
+}

@@ -196,7 +196,117 @@ SEB_BT_HD void bt_walk(const uint8_t *image, uint32_t num_pages, uint32_t root, 
     }
 }
 
-// ---- the host half (seb_btree.cpp).  0; -1 a null argument; -2 fewer than 4096 bytes or a wrong magic (bt_open);
+// ---- range scans: the leaf directory and what a scan computes from it.
+//
+// The directory of an image of num_pages pages is one flat buffer of bt_dir_bytes(num_pages) bytes, little-endian, whose
+// array offsets depend on num_pages alone (every array has room for num_pages leaves):
+//   [0, 32)            the header: u32 magic "BTDR", u32 num_pages, u32 root, u32 leaves L, u64 keys, u32 depth, u32 0
+//   32                 leaf[num_pages] u32: the reachable leaves' page ids in key order, 0 from entry L on
+//   bt_dir_first_at    first[num_pages + 1] u64: the exclusive prefix sum of the leaves' numCells, first[L] = keys, 0 behind
+//   bt_dir_ord_at      ord[num_pages] u32: a page's position in leaf[], kBtNoPage for a page that is no listed leaf
+// A refused image leaves a zeroed header, and nothing else in the buffer means anything.
+constexpr uint32_t kBtDirMagic = 0x42544452u;
+constexpr uint32_t kBtDirHeader = 32;
+
+struct BtDirInfo {  // seb_bt_dir_info
+    uint64_t leaves, keys;
+    uint32_t depth, reserved;
+};
+
+SEB_BT_HD uint64_t bt_dir_first_at(uint32_t num_pages) { return (kBtDirHeader + 4ull * num_pages + 7) & ~7ull; }
+SEB_BT_HD uint64_t bt_dir_ord_at(uint32_t num_pages) { return bt_dir_first_at(num_pages) + 8ull * num_pages + 8; }
+SEB_BT_HD uint64_t bt_dir_bytes(uint32_t num_pages) { return (bt_dir_ord_at(num_pages) + 4ull * num_pages + 15) & ~15ull; }
+
+struct BtDir {  // a directory's arrays; L and keys from its header, already held to L <= num_pages by who made this
+    const uint32_t *leaf;
+    const uint64_t *first;
+    const uint32_t *ord;
+    uint32_t num_pages, leaves;
+    uint64_t keys;
+};
+
+SEB_BT_HD BtDir bt_dir_view(const uint8_t *dir, uint32_t num_pages, uint32_t leaves, uint64_t keys) {
+    return BtDir{(const uint32_t *)(dir + kBtDirHeader), (const uint64_t *)(dir + bt_dir_first_at(num_pages)),
+                 (const uint32_t *)(dir + bt_dir_ord_at(num_pages)), num_pages, leaves, keys};
+}
+
+// The global position of a seek's answer (leaf, pos): first[ord[leaf]] + pos.  False where the seek ended in ERROR, at a
+// page the directory does not list, or past the leaf's cells.
+SEB_BT_HD bool bt_dir_position(const BtDir &d, const BtAnswer &a, uint64_t *g) {
+    if (a.status == kBtError || a.leaf >= d.num_pages) return false;
+    const uint32_t o = d.ord[a.leaf];
+    if (o >= d.leaves) return false;
+    const uint64_t lo = d.first[o], hi = d.first[o + 1];
+    if (hi < lo || a.pos > hi - lo) return false;
+    *g = lo + a.pos;
+    return true;
+}
+
+// One range's first position and count: start / end are the seeks' positions (0 and keys for an empty bound)
+SEB_BT_HD uint64_t bt_range_count(uint64_t first, uint64_t last, uint64_t limit) {
+    const uint64_t c = last > first ? last - first : 0;
+    return limit && c > limit ? limit : c;
+}
+
+// the last index of the non-decreasing x[0, n] (n + 1 entries, x[0] <= v) with x[index] <= v, held below n: a counted
+// bisection.  With x = first[] it is the leaf ordinal of global position v, with x = range_off[] the range of entry v.
+SEB_BT_HD uint64_t bt_upper_index(const uint64_t *x, uint64_t n, uint64_t v) {
+    uint64_t lo = 0, hi = n;  // the answer lies in [lo, hi)
+    for (uint32_t step = 0; step < 64 && lo + 1 < hi; ++step) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (x[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+struct BtEntry {  // one output entry of a scan
+    uint8_t status;
+    uint64_t kloc, vloc;
+    uint32_t klen, vlen;
+};
+
+// The cell at global position g: SEB_GET_FOUND with the key's and the value's place in the image, or SEB_GET_ERROR
+// with zero lengths where the directory's arrays or the page no longer give a cell.
+SEB_BT_HD BtEntry bt_scan_entry(const uint8_t *image, const BtDir &d, uint64_t g) {
+    BtEntry e{kBtError, 0, 0, 0, 0};
+    if (d.leaves == 0 || g >= d.keys) return e;
+    const uint64_t o = bt_upper_index(d.first, d.leaves, g);
+    const uint64_t lo = d.first[o];
+    const uint32_t p = d.leaf[o];
+    if (g < lo || g - lo > 0xFFFF || !bt_page_id_ok(p, d.num_pages)) return e;
+    const uint8_t *page = image + (uint64_t)p * kBtPage;
+    const uint32_t i = (uint32_t)(g - lo);
+    BtCell c;
+    if (page[0] != kBtLeaf || i >= bt_be16(page + 1) || !bt_cell(page, true, page[9] <= 1, i, &c)) return e;
+    e.status = kBtFound;
+    e.kloc = (uint64_t)p * kBtPage + c.koff, e.klen = c.klen;
+    e.vloc = (uint64_t)p * kBtPage + c.voff, e.vlen = c.vlen;
+    return e;
+}
+
+// The chain and order rules for listed leaf i (the directory's leaf[] and first[] already written): 0 good, 1 the
+// chain (RightPtr(leaf[i]) is not leaf[i + 1], or not 0 on the last leaf), 2 the order (the last key of this non-empty
+// leaf is not strictly below the first key of the next non-empty leaf, or one of the two does not parse).
+SEB_BT_HD uint32_t bt_leaf_link(const uint8_t *image, const BtDir &d, uint32_t i) {
+    const uint32_t p = d.leaf[i];
+    if (!bt_page_id_ok(p, d.num_pages)) return 1;
+    const uint8_t *page = image + (uint64_t)p * kBtPage;
+    if (bt_be32(page + 3) != (i + 1 < d.leaves ? d.leaf[i + 1] : 0)) return 1;
+    const uint64_t n = d.first[i + 1] - d.first[i];
+    if (n == 0) return 0;
+    uint32_t j = i + 1;
+    for (; j < d.leaves && d.first[j + 1] == d.first[j]; ++j) {}
+    if (j >= d.leaves) return 0;
+    const uint32_t q = d.leaf[j];
+    if (!bt_page_id_ok(q, d.num_pages)) return 2;
+    const uint8_t *next = image + (uint64_t)q * kBtPage;
+    BtCell a, b;
+    if (n > 0xFFFF || !bt_cell(page, true, page[9] <= 1, (uint32_t)n - 1, &a) || !bt_cell(next, true, next[9] <= 1, 0, &b)) return 2;
+    return bt_bytes_cmp(page + a.koff, a.klen, next + b.koff, b.klen) < 0 ? 0 : 2;
+}
+
+// ---- the host half (seb_btree.cpp, seb_btscan.cpp).  0; -1 a null argument; -2 fewer than 4096 bytes or a wrong magic (bt_open);
 // -3 meta.num_pages pages do not fit the image; -4 out of memory
 struct BtKeys {  // host memory, validated by the caller
     const uint8_t *data;
@@ -209,5 +319,43 @@ int bt_open(const uint8_t *image, uint64_t image_bytes, BtMeta *meta);
 int bt_check(const uint8_t *image, uint64_t image_bytes, const BtMeta &meta, uint8_t *kind, uint8_t *level, BtStats *stats);
 int bt_get(const uint8_t *image, uint64_t image_bytes, const BtMeta &meta, const BtKeys &keys, uint8_t *status, uint32_t *leaf,
            uint32_t *pos, uint64_t *vloc, uint32_t *vlen);
+
+// ---- seb_btscan.cpp.  The directory's refusals, in the order they are tested; each names a page.
+enum : int {
+    kDirRoot = 1,   // the root lies outside [1, num_pages)
+    kDirBad,        // a listed page that the check calls bad (or whose id lies outside the image)
+    kDirLevel,      // a page listed in round r whose level is not r
+    kDirMixed,      // a round lists leaves and internal pages: leaves at two levels
+    kDirDeep,       // internal pages in the last round the walk reaches
+    kDirWide,       // a level whose children number more than num_pages
+    kDirTwice,      // a leaf listed twice
+    kDirChain,      // RightPtr(leaf[i]) != leaf[i + 1], or the last leaf's is not 0
+    kDirOrder,      // the keys do not increase across a leaf boundary
+};
+const char *bt_dir_rule_text(int rule);
+// -5: refused, *rule and *page say why; dir: bt_dir_bytes(num_pages) bytes, 8-byte aligned; kind / level: bt_check's
+int bt_dir_build(const uint8_t *image, uint64_t image_bytes, const BtMeta &meta, const uint8_t *kind, const uint8_t *level,
+                 uint8_t *dir, BtDirInfo *info, int *rule, uint32_t *page);
+// the header of `dir` against meta: false where it is no directory of this image
+bool bt_dir_header_ok(const uint8_t *hdr32, const BtMeta &meta, uint32_t *leaves, uint64_t *keys);
+
+struct BtScanSizes {  // seb_bt_scan_sizes
+    uint64_t ranges, entries, key_bytes, val_bytes;
+};
+struct BtScanOut {  // host memory; entry arrays of entry_cap elements, offsets of entry_cap + 1, all nullable with cap 0
+    uint8_t *range_status;  // ranges
+    uint64_t *range_off;    // ranges + 1
+    uint8_t *status, *source;
+    uint64_t *kloc, *vloc;
+    uint32_t *klen, *vlen;
+    uint64_t entry_cap;
+    uint64_t *key_off, *val_off;
+    uint8_t *keys, *vals;
+    uint64_t key_cap, val_cap;
+};
+// -6: dir is no directory of this image; -7: a cap is below the need (*sizes filled for the retry; range_status and
+// range_off are written all the same); -8: 2^32 entries or more
+int bt_scan(const uint8_t *image, uint64_t image_bytes, const BtMeta &meta, const uint8_t *dir, const BtKeys &starts,
+            const BtKeys &ends, uint64_t limit, const BtScanOut &out, BtScanSizes *sizes);
 
 }  // namespace seb

@@ -25,7 +25,7 @@
 #include <stdint.h>
 
 #include "seb_btree.h"
-#include "seb_hidx_dev.h"  // ld_u64_le, prefix_words, u64a and the agent-scope atomics' spelling
+#include "seb_btree_dev.h"  // DevCmp; seb_hidx_dev.h's ld_u64_le, prefix_words, u64a and the agent-scope atomics' spelling
 #include "seb_kernels.h"
 
 #ifndef SEB_BT_LDS_ROOT
@@ -123,17 +123,6 @@ __global__ __launch_bounds__(256) void k_bt_stats(const uint8_t *__restrict__ im
         if (leaf_lo_inv) __hip_atomic_fetch_max(counts + bLeafLoInv, (u64a)leaf_lo_inv, HIDX_RLX_AGENT);
     }
 }
-
-struct DevCmp {  // the sign of bytes.Compare(key, stored): the prefix words first, the tails only on equal prefixes
-    const uint8_t *key;
-    uint32_t klen;
-    uint64_t k0, k1;
-    __device__ __forceinline__ int operator()(const uint8_t *stored, uint32_t slen) const {
-        uint64_t be[2];
-        prefix_words(stored, slen, be[0], be[1]);
-        return cmp_key(key, klen, k0, k1, be, stored, slen);
-    }
-};
 
 struct BtOut {
     uint8_t *status;

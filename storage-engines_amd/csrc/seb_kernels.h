@@ -455,6 +455,26 @@ hipError_t launch_bt_check(const uint8_t *image, uint32_t num_pages, uint32_t ro
 hipError_t launch_bt_get(const uint8_t *image, uint32_t num_pages, uint32_t root, const KeyBatch &kb, uint8_t *status,
                          uint32_t *leaf, uint32_t *pos, uint64_t *vloc, uint32_t *vlen, uint8_t *source, hipStream_t s);
 
+// The B-tree's range scans (seb_btscan.hip).  The directory's workspace: bt_dir_ws_bytes(num_pages)
+// bytes, 16-byte aligned; launch_bt_dir_build synchronises (a read-back per level) and fills *info_host, or *rule_host
+// (seb_btree.h's kDir*, 0 for none) and *page_host where it refuses; dir: bt_dir_bytes(num_pages) bytes, 8-byte aligned.
+// The scan's plan lives in a workspace of bt_scan_ws_bytes(ranges) bytes, 8-byte aligned: a 256-byte header, first_r,
+// range_off, the tiles' sums.  launch_bt_scan_plan (ranges >= 1) synchronises; launch_bt_scan_cells writes nothing
+// unless ws holds the plan of (ranges, entries), and nothing outside range_off[ranges + 1] and the entries' elements.
+struct BtDirInfo;
+uint32_t bt_dir_tile();
+uint64_t bt_dir_ws_bytes(uint32_t num_pages);
+hipError_t launch_bt_dir_build(const uint8_t *image, uint32_t num_pages, uint32_t root, const uint8_t *kind, const uint8_t *level,
+                               uint8_t *dir, void *ws, BtDirInfo *info_host, int *rule_host, uint32_t *page_host, hipStream_t s);
+uint64_t bt_scan_ws_bytes(uint64_t ranges);
+hipError_t bt_scan_read_dir(const uint8_t *dir, uint8_t head_host[32], hipStream_t s);
+hipError_t launch_bt_scan_plan(const uint8_t *image, uint32_t num_pages, uint32_t root, const uint8_t *dir, const KeyBatch &starts,
+                               const KeyBatch &ends, uint64_t limit, void *ws, uint8_t *range_status, uint64_t *entries_host,
+                               hipStream_t s);
+hipError_t launch_bt_scan_cells(const uint8_t *image, uint32_t num_pages, uint32_t root, const uint8_t *dir, uint64_t ranges,
+                                uint64_t entries, const void *ws, uint64_t *range_off, uint8_t *status, uint8_t *source,
+                                uint64_t *kloc, uint32_t *klen, uint64_t *vloc, uint32_t *vlen, hipStream_t s);
+
 // Process-wide tuning knobs (seb_set_option): the auto-dispatch thresholds, the build algorithm,
 // and the few shape choices tests force to cover both paths.  Variants measured slower were
 // removed from the kernels (DESIGN.md 8 keeps their numbers).
@@ -491,7 +511,7 @@ struct Options {
 Options &options();
 
 // The grid of a 256-lane grid-stride launch over `items` >= 1: a workgroup per 256 items, at most `most` of them and
-// at most options().grid_cap (seb_blockids.hip, seb_hashindex.hip, seb_hashwrite.hip, seb_btree.hip, seb_values.hip's
+// at most options().grid_cap (seb_blockids.hip, seb_hashindex.hip, seb_hashwrite.hip, seb_btree.hip, seb_btscan.hip, seb_values.hip's
 // copy and seb_codec.hip's k_route, whose ceiling is 65,536).  The default grid_cap lies above every ceiling, so a
 // default launch has min(ceil(items / 256), most) workgroups; a test sets grid_cap to 1 or 2 and the kernels' loops
 // take many trips on a small input.  Only for kernels whose workgroups never wait for one another.

@@ -126,6 +126,20 @@ class seb_bt_stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class seb_bt_dir_info(C.Structure):
+    _fields_ = [("leaves", C.c_uint64), ("keys", C.c_uint64), ("depth", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class seb_bt_scan_sizes(C.Structure):
+    _fields_ = [("ranges", C.c_uint64), ("entries", C.c_uint64), ("key_bytes", C.c_uint64), ("val_bytes", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.ranges, self.entries, self.key_bytes, self.val_bytes)
+
+
 class seb_run(C.Structure):
     """A sorted run in the builder's input layout (the memtable lookup): host or device pointers per entry point."""
     _fields_ = [("keys", C.c_void_p), ("key_bytes", C.c_uint64), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
@@ -317,6 +331,17 @@ _SIGS = {
     "seb_dev_bt_check": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, _vp, C.POINTER(seb_bt_stats), _vp]),
     "seb_dev_bt_get": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), C.POINTER(seb_keys), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_bt_load": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.POINTER(seb_bt_meta), C.POINTER(seb_bt_stats)]),
+    "seb_bt_dir_bytes": (_u64, [_u32]),
+    "seb_bt_dir_build": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, _vp, _vp, C.POINTER(seb_bt_dir_info)]),
+    "seb_bt_scan": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, C.POINTER(seb_keys), C.POINTER(seb_keys), _u64, _vp, _vp,
+                         _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(seb_bt_scan_sizes)]),
+    "seb_dev_bt_dir_workspace_size": (_u64, [_u32]),
+    "seb_dev_bt_dir_build": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, _vp, _vp, _vp, _u64, C.POINTER(seb_bt_dir_info), _vp]),
+    "seb_dev_bt_scan_workspace_size": (_u64, [_u64]),
+    "seb_dev_bt_scan_plan": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, C.POINTER(seb_keys), C.POINTER(seb_keys), _u64, _vp,
+                                  _vp, _u64, C.POINTER(seb_bt_scan_sizes), _vp]),
+    "seb_dev_bt_scan_cells": (_i, [_vp, _u64, C.POINTER(seb_bt_meta), _vp, C.POINTER(seb_bt_scan_sizes), _vp, _u64, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "seb_dev_pack_residues": (_i, [C.POINTER(seb_keys), _u64, _u32, _vp, _vp]),
     "seb_dev_probe_packed": (_i, [_vp, _u64, _vp, _u64, _u32, _vp, _vp]),
     "seb_dev_probe_emit_packed": (_i, [C.POINTER(seb_keys), _vp, _u64, _u32, _vp, _vp, _vp]),
@@ -2599,6 +2624,120 @@ def dev_bt_get(image, image_bytes: int, meta: seb_bt_meta, keys: seb_keys, statu
                                _ptr(vloc), _ptr(vlen), _ptr(source), _stream(stream)))
 
 
+# ------------------------------- B-tree, range scans: the leaf directory, Scan of a batch of ranges (btree/iterator.go)
+
+def bt_dir_bytes(num_pages: int) -> int:
+    return lib().seb_bt_dir_bytes(num_pages)
+
+
+def bt_dir_build(image, meta: seb_bt_meta, kind, level):
+    """The leaf directory of a checked image on the host: (dir u8 of bt_dir_bytes(meta.num_pages), info dict with
+    leaves, keys, depth).  kind / level: bt_check's arrays.  A refused image raises SebError (INVALID) naming the
+    page.  The reference for dev_bt_dir_build: both write the same bytes."""
+    img = _bytes_arg(image)
+    kd, lv = np.ascontiguousarray(kind, dtype=np.uint8), np.ascontiguousarray(level, dtype=np.uint8)
+    if kd.size < meta.num_pages or lv.size < meta.num_pages:
+        raise ValueError(f"kind / level hold {kd.size} / {lv.size} bytes, the image has {meta.num_pages} pages")
+    d = np.zeros(bt_dir_bytes(meta.num_pages) // 8, np.uint64).view(np.uint8)
+    info = seb_bt_dir_info()
+    check(lib().seb_bt_dir_build(_np_ptr(img), img.size, C.byref(meta), _np_ptr(kd), _np_ptr(lv), _np_ptr(d), C.byref(info)))
+    return d, info.as_dict()
+
+
+def _bound_keys(keys) -> HostKeys:
+    """A batch of bounds: every one may be empty, and a batch without a byte still needs a data pointer."""
+    kb = as_keys(keys)
+    if kb.offsets is not None and kb.data.size == 0:
+        kb = HostKeys(np.zeros(1, np.uint8), kb.offsets)
+    return kb
+
+
+def bt_scan(image, meta: seb_bt_meta, dir, starts, ends, limit: int = 0, caps=None):
+    """BTree.Scan for a batch of ranges [start, end) on the host (an empty start: from the first key; an empty end:
+    unbounded; limit 0: none).  Returns a dict: range_status (u8), range_off (u64, R + 1), the entries' status, source,
+    kloc, klen, vloc, vlen, the dense key_off / keys and val_off / vals, and sizes = (ranges, entries, key_bytes,
+    val_bytes).  caps = (entry_cap, key_cap, val_cap) sizes the outputs instead of a sizing call: below the need it
+    raises SebError (RANGE) with `.sizes` set for the retry.  The reference for dev_bt_scan_plan / _cells."""
+    img = _bytes_arg(image)
+    d = np.ascontiguousarray(dir, dtype=np.uint8)
+    ks, ke = _bound_keys(starts), _bound_keys(ends)
+    R = ks.n
+    rs, ro = np.zeros(R, np.uint8), np.zeros(R + 1, np.uint64)
+    sz = seb_bt_scan_sizes()
+    head = (_np_ptr(img), img.size, C.byref(meta), _np_ptr(d), ks.ref, ke.ref, limit, _np_ptr(rs), _np_ptr(ro))
+    if caps is None:
+        rc = lib().seb_bt_scan(*head, None, None, None, None, None, None, 0, None, None, 0, None, None, 0, C.byref(sz))
+        if rc < 0 and not (rc == -4 and sz.entries < 2**32):
+            raise SebError(rc, last_error())
+        caps = (sz.entries, sz.key_bytes, sz.val_bytes)
+    ec, kc, vc = caps
+    st, so = np.zeros(ec, np.uint8), np.zeros(ec, np.uint8)
+    kl, vl = np.zeros(ec, np.uint64), np.zeros(ec, np.uint64)
+    kn, vn = np.zeros(ec, np.uint32), np.zeros(ec, np.uint32)
+    ko, vo = np.zeros(ec + 1, np.uint64), np.zeros(ec + 1, np.uint64)
+    kb, vb = np.zeros(max(kc, 1), np.uint8), np.zeros(max(vc, 1), np.uint8)
+    rc = lib().seb_bt_scan(*head, _np_ptr(st), _np_ptr(so), _np_ptr(kl), _np_ptr(kn), _np_ptr(vl), _np_ptr(vn), ec, _np_ptr(ko),
+                           _np_ptr(kb), kc, _np_ptr(vo), _np_ptr(vb), vc, C.byref(sz))
+    if rc < 0:
+        err = SebError(rc, last_error())
+        err.sizes = sz.as_tuple()
+        raise err
+    n = sz.entries
+    return dict(range_status=rs, range_off=ro, status=st[:n], source=so[:n], kloc=kl[:n], klen=kn[:n], vloc=vl[:n], vlen=vn[:n],
+                key_off=ko[: n + 1], keys=kb[: sz.key_bytes], val_off=vo[: n + 1], vals=vb[: sz.val_bytes], sizes=sz.as_tuple())
+
+
+def dev_bt_dir_workspace_size(num_pages: int) -> int:
+    return lib().seb_dev_bt_dir_workspace_size(num_pages)
+
+
+def dev_bt_dir_build(image, image_bytes: int, meta: seb_bt_meta, kind, level, dir, ws, ws_bytes: int | None = None,
+                     stream=None) -> dict:
+    """The leaf directory of a checked device image into `dir` (u8 tensor of bt_dir_bytes(meta.num_pages), 8-byte
+    aligned); kind / level as dev_bt_check wrote them; ws: dev_bt_dir_workspace_size(meta.num_pages) bytes, 16-byte
+    aligned.  Synchronises; returns the info dict; a refused image raises SebError (INVALID) naming the page."""
+    for name, t, size in (("kind", kind, meta.num_pages), ("level", level, meta.num_pages), ("dir", dir, bt_dir_bytes(meta.num_pages))):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, {meta.num_pages} pages need {size}")
+    info = seb_bt_dir_info()
+    check(lib().seb_dev_bt_dir_build(_ptr(image), image_bytes, C.byref(meta), _ptr(kind), _ptr(level), _ptr(dir), _ptr(ws),
+                                     (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes, C.byref(info),
+                                     _stream(stream)))
+    return info.as_dict()
+
+
+def dev_bt_scan_workspace_size(ranges: int) -> int:
+    return lib().seb_dev_bt_scan_workspace_size(ranges)
+
+
+def dev_bt_scan_plan(image, image_bytes: int, meta: seb_bt_meta, dir, starts: seb_keys, ends: seb_keys, limit: int,
+                     range_status, ws, ws_bytes: int | None = None, stream=None) -> seb_bt_scan_sizes:
+    """Sizes a batch of ranges (device key batches of equal n): range_status (u8, n) is written, the plan goes into
+    `ws` (dev_bt_scan_workspace_size(n) bytes, 8-byte aligned).  Synchronises; returns the sizes (.ranges, .entries)
+    that dev_bt_scan_cells takes.  2^32 entries or more: SebError (RANGE)."""
+    if range_status is not None and _nbytes(range_status) < starts.n:
+        raise ValueError(f"range_status holds {_nbytes(range_status)} bytes, {starts.n} ranges")
+    sz = seb_bt_scan_sizes()
+    check(lib().seb_dev_bt_scan_plan(_ptr(image), image_bytes, C.byref(meta), _ptr(dir), C.byref(starts), C.byref(ends), limit,
+                                     _ptr(range_status), _ptr(ws), (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes,
+                                     C.byref(sz), _stream(stream)))
+    return sz
+
+
+def dev_bt_scan_cells(image, image_bytes: int, meta: seb_bt_meta, dir, sizes: seb_bt_scan_sizes, ws, range_off, status, source,
+                      kloc, klen, vloc, vlen, ws_bytes: int | None = None, stream=None) -> None:
+    """Writes range_off (u64, ranges + 1) and per entry status / source (u8), kloc / vloc (u64), klen / vlen (u32) from
+    the plan in `ws`: the arrays dev_get_values_* take with the image as pool.  Not synchronised."""
+    n = sizes.entries
+    for name, t, size in (("range_off", range_off, 8 * (sizes.ranges + 1)), ("status", status, n), ("source", source, n),
+                          ("kloc", kloc, 8 * n), ("klen", klen, 4 * n), ("vloc", vloc, 8 * n), ("vlen", vlen, 4 * n)):
+        if t is not None and _nbytes(t) < size:
+            raise ValueError(f"{name} holds {_nbytes(t)} bytes, the plan needs {size}")
+    check(lib().seb_dev_bt_scan_cells(_ptr(image), image_bytes, C.byref(meta), _ptr(dir), C.byref(sizes), _ptr(ws),
+                                      (_nbytes(ws) if ws is not None else 0) if ws_bytes is None else ws_bytes, _ptr(range_off),
+                                      _ptr(status), _ptr(source), _ptr(kloc), _ptr(klen), _ptr(vloc), _ptr(vlen), _stream(stream)))
+
+
 def _ctx_bt_load(self, image, dev_image, dev_kind=None, dev_level=None, cap: int | None = None):
     """seb_bt_load: a host image opened, uploaded into dev_image and checked.  Returns (meta, stats dict)."""
     img = _bytes_arg(image)
@@ -2614,19 +2753,22 @@ Ctx.bt_load = _ctx_bt_load
 
 class BTreeImage:
     """The read side of the reference's B-tree on one device: the page-file image lives in device memory.
-    open(image) is readMetadata + upload + the structural check; check() runs the check again; get_batch(keys) is
-    BTree.Get for a batch, ending in the values gather (dev_get_values_*) with the image as its pool."""
+    open(image) is readMetadata + upload + the structural check + the leaf directory; check() runs the check again;
+    get_batch(keys) is BTree.Get for a batch, ending in the values gather (dev_get_values_*) with the image as its pool;
+    scan_batch(starts, ends) is BTree.Scan for a batch of ranges through the directory, ending in two such gathers.
+    An image whose directory is refused still opens: `dir` is None, `dir_error` keeps the message, get_batch works."""
 
     def __init__(self, device: int = 0):
         self._ctx = Ctx(device)
         self.device = device
         self.image = self.kind = self.level = self.meta = None
+        self.dir, self.dir_info, self.dir_error = None, {}, None
         self.image_bytes = 0
         self.stats = {}
 
     def close(self):
         self._ctx.close()
-        self.image = self.kind = self.level = None
+        self.image = self.kind = self.level = self.dir = None
 
     def open(self, image) -> dict:
         """The file's bytes (what Sync wrote, any WAL already applied).  Returns the check's stats; `meta`, `kind`
@@ -2640,11 +2782,80 @@ class BTreeImage:
         self.level = torch.empty(max(pages, 1), dtype=torch.uint8, device=dev)
         self.meta, self.stats = self._ctx.bt_load(img, self.image, self.kind, self.level)
         self.image_bytes = self.meta.num_pages * BT_PAGE_BYTES
+        self._build_dir()
         return self.stats
+
+    def _build_dir(self):
+        import torch
+        dev, pages = self.image.device, self.meta.num_pages
+        d = torch.empty(bt_dir_bytes(pages), dtype=torch.uint8, device=dev)
+        ws = torch.empty(dev_bt_dir_workspace_size(pages), dtype=torch.uint8, device=dev)
+        self.dir, self.dir_info, self.dir_error = None, {}, None
+        try:
+            self.dir_info = dev_bt_dir_build(self.image, self.image_bytes, self.meta, self.kind, self.level, d, ws)
+            self.dir = d
+        except SebError as e:
+            if e.code != -1:
+                raise
+            self.dir_error = str(e)
 
     def check(self) -> dict:
         self.stats = dev_bt_check(self.image, self.image_bytes, self.meta, self.kind, self.level)
         return self.stats
+
+    def _dev_keys(self, keys):
+        import torch
+        kb = as_keys(keys)
+        dev = self.image.device
+        data = torch.from_numpy(kb.data.reshape(-1).copy() if kb.data.size else np.zeros(1, np.uint8)).to(dev)
+        if kb.offsets is not None:
+            return dev_keys(data, torch.from_numpy(kb.offsets.view(np.int64).copy()).to(dev))
+        return dev_keys(data, n=kb.n, stride=kb.stride)
+
+    def _gather(self, status, source, loc, length, n):
+        import torch
+        dev = self.image.device
+        ws = torch.empty(dev_get_values_workspace_size(n), dtype=torch.uint8, device=dev)
+        sz = dev_get_values_plan(status, source, None, loc, length, n, [], self.image, ws, pool_bytes=self.image_bytes)
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        out = torch.empty(max(sz.val_bytes, 1), dtype=torch.uint8, device=dev)
+        dev_get_values_emit(status, source, None, loc, length, n, [], self.image, sz, ws, off, out if sz.val_bytes else None,
+                            pool_bytes=self.image_bytes)
+        return off, out, sz.val_bytes
+
+    def scan_batch(self, starts, ends, limit: int = 0):
+        """BTree.Scan for a batch of ranges [start, end) (anything as_keys takes; an empty start: from the first key;
+        an empty end: unbounded; limit 0: none): (range_status u8, range_off u64 R + 1, key_off u64, keys u8, val_off
+        u64, vals u8).  Range r's entries are [range_off[r], range_off[r + 1]); entry e's key is keys[key_off[e]:
+        key_off[e + 1]], its value vals[val_off[e]: val_off[e + 1]].  range_status[r] == GET_ERROR: a bound's walk met a
+        page the image does not hold whole.  Raises SebError where the image's directory was refused."""
+        import torch
+        if self.dir is None:
+            raise SebError(-1, self.dir_error or "BTreeImage.scan_batch: no image is open")
+        ks, ke = self._dev_keys(starts), self._dev_keys(ends)
+        R = ks.n
+        dev = self.image.device
+        zero = np.zeros(1, np.uint64)
+        if R == 0:
+            return np.zeros(0, np.uint8), zero, zero.copy(), np.zeros(0, np.uint8), zero.copy(), np.zeros(0, np.uint8)
+        rs = torch.empty(R, dtype=torch.uint8, device=dev)
+        ws = torch.empty(dev_bt_scan_workspace_size(R), dtype=torch.uint8, device=dev)
+        sz = dev_bt_scan_plan(self.image, self.image_bytes, self.meta, self.dir, ks, ke, limit, rs, ws)
+        n = sz.entries
+        ro = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        st, so = torch.empty(max(n, 1), dtype=torch.uint8, device=dev), torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        kl, vl = torch.empty(max(n, 1), dtype=torch.int64, device=dev), torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        kn, vn = torch.empty(max(n, 1), dtype=torch.int32, device=dev), torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        dev_bt_scan_cells(self.image, self.image_bytes, self.meta, self.dir, sz, ws, ro, st, so, kl, kn, vl, vn)
+        if n == 0:
+            torch.cuda.synchronize(dev)
+            return (rs.cpu().numpy(), ro.cpu().numpy().view(np.uint64), zero, np.zeros(0, np.uint8), zero.copy(),
+                    np.zeros(0, np.uint8))
+        ko, kb, kbytes = self._gather(st, so, kl, kn, n)
+        vo, vb, vbytes = self._gather(st, so, vl, vn, n)
+        torch.cuda.synchronize(dev)
+        return (rs.cpu().numpy(), ro.cpu().numpy().view(np.uint64), ko.cpu().numpy().view(np.uint64), kb.cpu().numpy()[:kbytes],
+                vo.cpu().numpy().view(np.uint64), vb.cpu().numpy()[:vbytes])
 
     def get_batch(self, keys):
         """BTree.Get for a key batch (anything as_keys takes): (status u8, out_off u64 n + 1, out_vals u8): key i's
